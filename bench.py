@@ -15,7 +15,12 @@ Total work is fixed as N grows: "scaling": "strong".  `python bench.py --gpus N`
 without a launcher re-launches itself under torch.distributed.run (before any GPU
 call) and exits with its status.
 
-CPU legs (rank 0, N = 1, after the timed region):
+A plain run sets up, warms up, times --steps steps and prints the line.  --dump-outputs DIR
+also writes what the last timed step returned to its caller as DIR/<name>.npy.  Everything
+else (the CPU legs, the host-buffer path, the sharded path's phase breakdown and self-check)
+runs only with --full.
+
+CPU legs (--full; rank 0, N = 1, after the timed region):
   cpu_baseline       the khipu-faithful sequential trie (oracle/khipu_oracle.cc, 1 core)
                      on the first 20k/50k/100k/1M accounts of the same workload (--seq-samples);
                      every sample's root is asserted equal to the GPU root of the same prefix;
@@ -82,7 +87,35 @@ def parse():
     p.add_argument("--no-host-path", action="store_true", help="state: skip the host-buffer (PCIe) drop-in timing")
     p.add_argument("--tries", type=int, default=100_000, help="storage: storage tries per step")
     p.add_argument("--blocks", type=int, default=10_000, help="lists: blocks per step")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU legs (unless --no-cpu), the "
+                        "host-buffer path (unless --no-host-path), the sharded path's phase breakdown and self-check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    args = p.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_host_path = True
+    return args
+
+
+DUMP_BUDGET = 64 << 20  # bytes over all the files of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` ({name: ndarray}) as path/<name>.npy, bytes as
+    float32 and wider integers as float64 (both exact).  An array over its share of
+    DUMP_BUDGET is cut to a fixed, seeded sample of its rows, in order."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+        a = a.reshape(-1) if a.ndim == 0 else a
+        row = max(a[0].nbytes, 1) if len(a) else 1
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), share // row, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def cpu_model():
@@ -255,6 +288,10 @@ def verify(args):
     for _ in range(args.steps):
         call()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        t = int(total.value)
+        dump_outputs(args.dump_outputs, {"hash32": hh, "match": match, "status": status, "child_off": coff,
+                                         "child": child[:t], "child_kind": ckind[:t]})
     out = {"metric": "fast-sync NodeData values verified/s (kec256 + request match + PV63 decode)", "value": n / dt,
            "unit": "nodes/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64",
@@ -388,6 +425,8 @@ def single(args):
         stats.append(st.as_dict())
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:  # what ctx.build returned: the root reference (hash, encoded length, inline bytes)
+        dump_outputs(args.dump_outputs, {"hash32": hh, "enc_len": ll, "inline": ii})
     root = hh[0].tobytes()
     s = stats[-1]
     ms_dev = float(np.mean([x["t_total_ms"] for x in stats]))
@@ -462,6 +501,8 @@ def lists(args):
         roots, st = ctx.list_roots(d_items, d_off, so)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"roots": np.frombuffer(b"".join(roots), np.uint8).reshape(-1, 32)})
     s = st.as_dict()
     perms_leaf = s["n_leaves"]
     leaf_ms = s["t_leaf_ms"]
@@ -586,6 +627,8 @@ def storage(args):
         roots = np.concatenate([allr[g].cpu().numpy()[:bnd[g + 1] - bnd[g]] for g in range(world)])
     else:
         roots = hh
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"roots": roots})
     ok = torch.ones(1, dtype=torch.int64, device=f"cuda:{local}")
     res = None
     if rank == 0:

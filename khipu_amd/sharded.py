@@ -365,16 +365,21 @@ def bench_main(args):
             "traffic": bench.pmc_traffic_per_unit("k_leaf_in", slow[1]),
             "traffic_note": "HBM bytes per launch: the committed 100M PMC summary's bytes per leaf x this launch's leaves",
             "avg_ms": slow[0], "perms_per_launch": int(slow[1]), "rank": "slowest of the ranks"}
-    # one more (untimed) step with a device sync after every phase: where the time goes
-    phases = {}
-    sharded_root(be, addr, vals, voff, n, phases=phases)
-    ph = torch.tensor([phases[k] for k in sorted(phases)], dtype=torch.float64, device=f"cuda:{local}")
-    dist.all_reduce(ph, op=dist.ReduceOp.MAX)
-    phases = {k: round(float(v), 3) for k, v in zip(sorted(phases), ph.tolist())}
-    # self-check (after the timed region): a wrong root must not be reported as throughput
+    full = getattr(args, "full", False)
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        bench.dump_outputs(args.dump_outputs, {"state_root": np.frombuffer(root, np.uint8)})
+    # --full: one more (untimed) step with a device sync after every phase: where the time goes
+    phases = None
+    if full:
+        phases = {}
+        sharded_root(be, addr, vals, voff, n, phases=phases)
+        ph = torch.tensor([phases[k] for k in sorted(phases)], dtype=torch.float64, device=f"cuda:{local}")
+        dist.all_reduce(ph, op=dist.ReduceOp.MAX)
+        phases = {k: round(float(v), 3) for k, v in zip(sorted(phases), ph.tolist())}
+    # --full: self-check (after the timed region): a wrong root must not be reported as throughput
     ok = torch.ones(1, dtype=torch.int64, device=f"cuda:{local}")
     check = None
-    if rank == 0:
+    if rank == 0 and full:
         good, check = self_check(be, args.cfg, n_total, root)
         ok[0] = int(good)
     dist.broadcast(ok, 0)

@@ -10,5 +10,7 @@ for w in 2 4 8; do
   timeout -k 10 300 python scripts/shard_rank_sim.py --world $w > gpurun_out/shard_sim_${tag}_$w.json || exit 1
   cat gpurun_out/shard_sim_${tag}_$w.json
 done
-timeout -k 10 300 python bench.py --sharded --steps 5 --warmup 2 --no-cpu > gpurun_out/shard_bench_$tag.json 2> gpurun_out/shard_bench_$tag.err || { tail gpurun_out/shard_bench_$tag.err; exit 1; }
-python -c "import json;d=json.load(open('gpurun_out/shard_bench_$tag.json'));print(d['ms_per_step'], d['state_root'][:12], d['phase_ms_max_over_ranks'])"
+OUT=${OUT:-bench_out}  # where the bench line goes
+mkdir -p "$OUT"
+timeout -k 10 300 python bench.py --sharded --steps 5 --warmup 2 --full --no-cpu > "$OUT/shard_bench_$tag.json" 2> "$OUT/shard_bench_$tag.err" || { tail "$OUT/shard_bench_$tag.err"; exit 1; }
+python -c "import json;d=json.load(open('$OUT/shard_bench_$tag.json'));print(d['ms_per_step'], d['state_root'][:12], d['phase_ms_max_over_ranks'])"

@@ -67,6 +67,41 @@ def test_seq_root_hashes_keys_in_c(oracle):
         oracle.seq_root([oracle.kec256(x) for x in addrs], vals)
 
 
+def test_plain_run_has_no_extra_legs(monkeypatch):
+    """Without --full the CPU legs and the host-buffer path are off; --full turns them on,
+    and --no-cpu / --no-host-path still take single legs out of it."""
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+    a = parse("--gpus", "1", "--steps", "3", "--warmup", "1")
+    assert (a.steps, a.warmup, a.full, a.no_cpu, a.no_host_path, a.dump_outputs) == (3, 1, False, True, True, None)
+    a = parse("--full")
+    assert a.full and not a.no_cpu and not a.no_host_path and not a.no_cpu_batch
+    a = parse("--full", "--no-cpu", "--dump-outputs", "d")
+    assert a.full and a.no_cpu and not a.no_host_path and a.dump_outputs == "d"
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: bytes as float32, wider integers as float64, values exact; an array over
+    its share of the budget becomes the same seeded sample of rows on every call."""
+    import numpy as np
+    r = np.random.default_rng(2)
+    hh = r.integers(0, 256, (1, 32), dtype=np.uint8)
+    ll = np.array([2 ** 32 - 1, 532], np.uint32)
+    big = r.integers(0, 256, (1000, 32), dtype=np.uint8)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * 100 * 32 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"hash32": hh, "enc_len": ll, "big": big})
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("hash32", "enc_len", "big")}
+    assert got["hash32"].dtype == np.float32 and (got["hash32"] == hh).all()
+    assert got["enc_len"].dtype == np.float64 and (got["enc_len"] == ll).all()
+    assert got["big"].dtype == np.float32 and got["big"].shape == (100, 32)
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_BUDGET
+    rows = {x.tobytes() for x in big.astype(np.float32)}
+    assert all(x.tobytes() in rows for x in got["big"])
+    assert (np.load(tmp_path / "b" / "big.npy") == got["big"]).all()
+
+
 def test_storage_ranges_balanced():
     """bench.py --workload storage: slot-balanced contiguous trie ranges cover every trie once."""
     import numpy as np
