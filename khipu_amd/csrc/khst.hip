@@ -36,6 +36,7 @@
 #include "keyorder.h"
 #include "forest.h"
 #include "nodedata.h"
+#include "layout.h"
 
 using namespace khst;
 
@@ -1779,24 +1780,12 @@ struct DevBuf {
   }
 };
 
-// bump carving inside one DevBuf
-struct Carver {
-  char* base;
-  size_t off = 0;
-  size_t cap;
-  template <typename T>
-  T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* r = (T*)(base + off);
-    off += count * sizeof(T) + 16;  // +16: slack for 8-byte word over-reads
-    if (off > cap) throw KhError{KH_EINTERNAL, "workspace carve overflow"};
-    return r;
-  }
-};
-static size_t carve_size(const std::vector<size_t>& items) {
-  size_t s = 0;
-  for (size_t b : items) s = ((s + 255) & ~(size_t)255) + b + 16;
-  return s + 256;
+// the arrays carved out of one DevBuf, each declared once (layout.h)
+[[noreturn]] static void layout_fail(const char* msg) { throw KhError{KH_EINTERNAL, msg}; }
+using Layout = BasicLayout<layout_fail>;
+static void place(DevBuf& b, const Layout& L) {
+  b.ensure(L.bytes());
+  L.place(b.p, b.cap);
 }
 
 struct BuildInfo {  // the last build's sizes, for build_stats
@@ -2128,6 +2117,18 @@ struct SortIO {
   uint64_t m;
   uint32_t* sidx;
   bool fallback;
+  // Declares the sort's scratch into the caller's workspace: nk keys and their indices, skey of
+  // skey_words words, sseg for a segmented sort, the radix and scan scratch for radix_n and
+  // scan_n entries, and ctr_n counters (0: ctr is part of the caller's own counter block)
+  void declare(Layout& L, uint64_t nk, uint64_t skey_words, bool segmented, uint64_t radix_n, uint64_t scan_n,
+               uint64_t ctr_n) {
+    L.add_all(nk, ck0, ck1, idx0, idx1);
+    L.add(skey, skey_words);
+    L.add(sseg, nk, segmented);
+    L.add(rs_scratch, radix_scratch_bytes(radix_n));
+    L.add(scan_scratch, scan_scratch_bytes(scan_n, 8));
+    if (ctr_n) L.add(ctr, ctr_n);
+  }
 };
 static void sort_dedup(kh_ctx* c, SortIO& S) {
   hipStream_t st = c->st;
@@ -2188,10 +2189,9 @@ static void sort_dedup(kh_ctx* c, SortIO& S) {
         HIPCHK(hipMemcpyAsync(c->h_pinned, mtot, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         m = (uint32_t)c->h_pinned[0];
-        c->ws3.ensure(carve_size({n * 4, n * 4}));
-        Carver c3{(char*)c->ws3.p, 0, c->ws3.cap};
-        ock = c3.take<uint32_t>(n);
-        oidx = c3.take<uint32_t>(n);
+        Layout L3;
+        L3.add_all(n, ock, oidx);
+        place(c->ws3, L3);
         hipLaunchKernelGGL(k_compact_ck, GRID(n, BS), dim3(BS), 0, st, (const uint32_t*)c32, (const uint32_t*)idxs,
                            (const uint32_t*)keep_pos, (const uint32_t*)keep, n, ock, oidx);
         LAUNCH_CHECK();
@@ -2310,11 +2310,13 @@ static void sort_dedup(kh_ctx* c, SortIO& S) {
       m = n - ndup;
     }
     if (m < n) {
-      c->ws3.ensure(carve_size({n * 32, n * 4, n * 4}));
-      Carver c3{(char*)c->ws3.p, 0, c->ws3.cap};
-      uint64_t* skey2 = c3.take<uint64_t>(n * 4);
-      uint32_t* sidx2 = c3.take<uint32_t>(n);
-      uint32_t* sseg2 = segmented ? c3.take<uint32_t>(n) : nullptr;
+      Layout L3;
+      uint64_t* skey2;
+      uint32_t *sidx2, *sseg2;
+      L3.add(skey2, n * 4);
+      L3.add_all(n, sidx2, sseg2);
+      place(c->ws3, L3);
+      if (!segmented) sseg2 = nullptr;  // (carved all the same)
       hipLaunchKernelGGL(k_compact, GRID(n, BS), dim3(BS), 0, st, (const uint64_t*)skey, (const uint32_t*)sidx,
                          (const uint32_t*)sseg, (const uint32_t*)keep_pos, (const uint32_t*)keep, n, skey2, sidx2,
                          sseg2);
@@ -2379,106 +2381,60 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   const uint64_t nb1 = n;  // boundaries <= n-1; round up
   // keys are moved as 16-byte vectors: caller keys that are not 16-byte aligned get copied
   const bool own_keys = (A.flags & KH_HASH_KEYS) || ((uintptr_t)A.keys & 15);
-  std::vector<size_t> sz = {
-      own_keys ? n * 32 : 0,                  // K32
-      n * 8, n * 8, n * 4, n * 4,             // ck0 ck1 idx0 idx1
-      n * 32, segmented ? n * 4 : 0,          // skey sseg
-      radix_scratch_bytes(n), scan_scratch_bytes(n, 8),
-      nb1, nb1 / 32 + 1024,                   // u, pyramid
-      nb1 * 4, nb1 * 4, nb1 * 4, nb1 * 4, nb1, nb1 * 4, nb1, nb1,  // psv nsv pse rep ord isrep glast gk
-      nb1 * 4, nb1 * 4, nb1, nb1, nb1 * 4, nb1, nb1 * 4, nb1 * 8, nb1 * 4, nb1 * 4,  // branches
-      n * 4, n, n, n * 8, n * 4, n * 8, n * 4,  // leaves, svoff, svlen
-      A.emit ? n * 32 : 0, A.emit ? nb1 * 32 : 0, A.emit ? nb1 * 32 : 0,  // hashes
-      nres * 32, nres * 4, nres * 32,         // results
-      CTR_N * CTR_SHARDS * 8, 64 * 4, 80 * 4, 64 * 4, NBUCKET * ((nb1 + LV_TILE - 1) / LV_TILE) * 4, nb1 * 4,  // ctr hist lb bcnt order
-      early ? n * 32 : 0, early ? n : 0, early ? n * 8 : 0,  // early leaves: stashed references, meta, pd|position
-      early && !lpos ? n * 8 : 0,                                 // link slots (segmented early builds)
-      A.kn ? n : 0,                           // sorted key lengths
-      nb1 * 4, nb1 * 4, nb1 * 4, nb1, nb1, nb1,  // branch tables in key-order ids (BrTab J)
-      lpos ? nb1 * 4 : 0, lpos ? nb1 * 4 : 0, lpos ? n * 4 : 0,  // leaf positions: range ends (J, T), long list
-      nb1 * 4, nb1 * 4,                       // tile topology: boundaries left to the whole-array ANSV / chain
-  };
-  c->ws1.ensure(carve_size(sz));
-  Carver cv{(char*)c->ws1.p, 0, c->ws1.cap};
-  uint64_t* K32 = own_keys ? cv.take<uint64_t>(n * 4) : (uint64_t*)A.keys;
-  uint64_t* ck0 = cv.take<uint64_t>(n);
-  uint64_t* ck1 = cv.take<uint64_t>(n);
-  uint32_t* idx0 = cv.take<uint32_t>(n);
-  uint32_t* idx1 = cv.take<uint32_t>(n);
-  uint64_t* skey = cv.take<uint64_t>(n * 4);
-  uint32_t* sseg = segmented ? cv.take<uint32_t>(n) : nullptr;
-  void* rs_scratch = cv.take<char>(radix_scratch_bytes(n));
-  void* scan_scratch = cv.take<char>(scan_scratch_bytes(n, 8));
+  Layout L;
+  uint64_t* K32;
+  uint8_t *pyr, *skn;
+  uint32_t *lb, *wcnt, *bcnt, *order, *tlist_a, *tlist_c;
+  L.add(K32, n * 4, own_keys);
+  SortIO S{nullptr, A.seg, sb, n};  // (K32 and ctr -- T.ctr, in the block zeroed below -- once placed)
+  S.declare(L, n, n * 4, segmented, n, n, 0);
   Topo T{};
-  T.u = cv.take<uint8_t>(nb1);
-  uint8_t* pyr = cv.take<uint8_t>(nb1 / 32 + 1024);
-  T.psv = cv.take<int32_t>(nb1);
-  T.nsv = cv.take<int32_t>(nb1);
-  T.pse = cv.take<int32_t>(nb1);
-  T.rep = cv.take<uint32_t>(nb1);
-  T.ord = cv.take<uint8_t>(nb1);
-  T.isrep_bid = cv.take<uint32_t>(nb1);
-  T.glast = cv.take<uint8_t>(nb1);
-  T.gk = cv.take<uint8_t>(nb1);
-  T.br_k = cv.take<uint32_t>(nb1);
-  T.br_cbase = cv.take<uint32_t>(nb1);
-  T.br_depth = cv.take<uint8_t>(nb1);
-  T.br_ext = cv.take<uint8_t>(nb1);
-  T.br_parent = cv.take<uint32_t>(nb1);
-  T.br_pord = cv.take<uint8_t>(nb1);
-  T.br_first = cv.take<uint32_t>(nb1);
-  T.br_aoff = cv.take<uint64_t>(nb1);
-  T.br_len = cv.take<uint32_t>(nb1);
-  T.ex_len = cv.take<uint32_t>(nb1);
-  T.lf_parent = cv.take<uint32_t>(n);
-  T.lf_pord = cv.take<uint8_t>(n);
-  T.lf_pd = cv.take<int8_t>(n);
-  T.lf_aoff = cv.take<uint64_t>(n);
-  T.lf_len = cv.take<uint32_t>(n);
-  T.svoff = cv.take<uint64_t>(n);
-  T.svlen = cv.take<uint32_t>(n);
-  T.lf_hash = A.emit ? cv.take<uint64_t>(n * 4) : nullptr;
-  T.br_hash = A.emit ? cv.take<uint64_t>(nb1 * 4) : nullptr;
-  T.ex_hash = A.emit ? cv.take<uint64_t>(nb1 * 4) : nullptr;
-  T.res_hash = cv.take<uint64_t>(nres * 4);
-  T.res_len = cv.take<uint32_t>(nres);
-  T.res_inl = cv.take<uint64_t>(nres * 4);
-  T.ctr = cv.take<unsigned long long>(CTR_N * CTR_SHARDS);
-  T.depth_hist = cv.take<uint32_t>(64);
-  uint32_t* lb = cv.take<uint32_t>(80);
-  uint32_t* wcnt = cv.take<uint32_t>(64);  // k_branch_wide: the wide branches of each level (zeroed below)
+  L.add(T.u, nb1);
+  L.add(pyr, nb1 / 32 + 1024);
+  L.add_all(nb1, T.psv, T.nsv, T.pse, T.rep, T.ord, T.isrep_bid, T.glast, T.gk);
+  L.add_all(nb1, T.br_k, T.br_cbase, T.br_depth, T.br_ext, T.br_parent, T.br_pord, T.br_first, T.br_aoff, T.br_len,
+            T.ex_len);
+  L.add_all(n, T.lf_parent, T.lf_pord, T.lf_pd, T.lf_aoff, T.lf_len, T.svoff, T.svlen);
+  L.add(T.lf_hash, n * 4, A.emit);
+  L.add(T.br_hash, nb1 * 4, A.emit);
+  L.add(T.ex_hash, nb1 * 4, A.emit);
+  // results, counters, depth histogram, level bounds, wide-branch counts: back to back (one
+  // memset, one copy each of the counters and of the results); their offsets from the results
+  const size_t o_res = L.add(T.res_hash, nres * 4);
+  const size_t o_len = L.add(T.res_len, nres) - o_res;
+  const size_t o_inl = L.add(T.res_inl, nres * 4) - o_res;
+  const size_t o_ctr = L.add(T.ctr, CTR_N * CTR_SHARDS) - o_res;
+  L.add(T.depth_hist, 64);
+  const size_t o_lb = L.add(lb, 80) - o_res;
+  L.add(wcnt, 64);  // k_branch_wide: the wide branches of each level (zeroed below)
+  const size_t o_wend = L.end() - o_res;
   const uint32_t nblk_max = (uint32_t)((nb1 + LV_TILE - 1) / LV_TILE);
-  uint32_t* bcnt = cv.take<uint32_t>((uint64_t)NBUCKET * nblk_max);
-  uint32_t* order = cv.take<uint32_t>(nb1);
-  T.lf_eref = early ? cv.take<uint64_t>(n * 4) : nullptr;
-  T.lf_emeta = early ? cv.take<uint8_t>(n) : nullptr;
-  T.pdinv = early ? cv.take<uint64_t>(n) : nullptr;
-  T.lf_dst = early && !lpos ? cv.take<uint64_t>(n) : nullptr;
+  L.add(bcnt, (uint64_t)NBUCKET * nblk_max);
+  L.add(order, nb1);
+  // early leaves: stashed references, meta, pd|position; link slots (segmented early builds)
+  L.add(T.lf_eref, n * 4, early);
+  L.add(T.lf_emeta, n, early);
+  L.add(T.pdinv, n, early);
+  L.add(T.lf_dst, n, early && !lpos);
+  L.add(skn, n, A.kn != nullptr);  // sorted key lengths
+  BrTab J{};  // branch tables in key-order ids
+  L.add_all(nb1, J.k, J.parent, J.first, J.depth, J.ext, J.pord);
+  // leaf positions: range ends (J, T), long list
+  L.add(J.end, nb1, lpos);
+  L.add(T.br_end, nb1, lpos);
+  L.add(T.longlist, n, lpos);
+  T.lpos = lpos ? 1 : 0;
+  L.add_all(nb1, tlist_a, tlist_c);  // tile topology: boundaries left to the whole-array ANSV / chain
+  place(c->ws1, L);
+  if (!own_keys) K32 = (uint64_t*)A.keys;
   T.kin = K32;
-  uint8_t* skn = A.kn ? cv.take<uint8_t>(n) : nullptr;
-  BrTab J{};
-  J.k = cv.take<uint32_t>(nb1);
-  J.parent = cv.take<uint32_t>(nb1);
-  J.first = cv.take<uint32_t>(nb1);
-  J.depth = cv.take<uint8_t>(nb1);
-  J.ext = cv.take<uint8_t>(nb1);
-  J.pord = cv.take<uint8_t>(nb1);
-  if (lpos) {
-    J.end = cv.take<uint32_t>(nb1);
-    T.br_end = cv.take<uint32_t>(nb1);
-    T.longlist = cv.take<uint32_t>(n);
-    T.lpos = 1;
-  }
-  uint32_t* tlist_a = cv.take<uint32_t>(nb1);
-  uint32_t* tlist_c = cv.take<uint32_t>(nb1);
   T.depth0 = A.depth0;
   T.segmented = segmented ? 1 : 0;
   T.vals = A.vals;
   T.voff = A.voff;
   T.vlen_in = A.vlen;
 
-  // results, counters, depth histogram and level bounds are carved back to back: one memset
-  HIPCHK(hipMemsetAsync(T.res_hash, 0, (size_t)((char*)(wcnt + 64) - (char*)T.res_hash), st));
+  HIPCHK(hipMemsetAsync(T.res_hash, 0, o_wend, st));
 
   // stage events (kh_stats' t_keys / t_sort / t_topo / t_leaf / t_branch): not for a forest's
   // element builds, whose host is the bottleneck (the block-commit HIP API trace: every API
@@ -2501,17 +2457,17 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   // land; every other path waits for all keys (and the value offsets)
   if (A.hs && !ck_ready) A.hs->stream_wait(st, A.hs->nkp);
   if (ck_ready) {
-    uint32_t* c0 = (uint32_t*)ck0;
+    uint32_t* c0 = (uint32_t*)S.ck0;
     const uint32_t parts = A.hs ? A.hs->nkp : 1;
     for (uint32_t p = 0; p < parts; ++p) {
       const uint64_t a = A.hs && p ? A.hs->kend[p - 1] : 0, b = A.hs ? A.hs->kend[p] : n;
       if (A.hs) A.hs->stream_wait(st, p);
       if (A.klen <= 135)
-        hipLaunchKernelGGL(k_hash_keys_ck<true>, GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0, idx0,
-                           A.seg, sb);
+        hipLaunchKernelGGL(k_hash_keys_ck<true>, GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0,
+                           S.idx0, A.seg, sb);
       else
-        hipLaunchKernelGGL(k_hash_keys_ck<false>, GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0, idx0,
-                           A.seg, sb);
+        hipLaunchKernelGGL(k_hash_keys_ck<false>, GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0,
+                           S.idx0, A.seg, sb);
       LAUNCH_CHECK();
     }
   } else if (A.flags & KH_HASH_KEYS) {
@@ -2531,37 +2487,28 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   // bits exact: only a run past the tie kernel, rare, redoes the build)
   const bool spec = (ck_path || (A.el && !A.kn)) && !A.no_spec && c->spec_off == 0;
   if (c->spec_off) --c->spec_off;
-  uint64_t m = n;
-  uint32_t* sidx = nullptr;
-  bool fallback = false;
-  bool ties_u = false, all_u = false;
-  {
-    SortIO S{(const uint64_t*)K32, A.seg, sb, n, ck0, ck1, idx0, idx1, skey, sseg, rs_scratch, scan_scratch, T.ctr,
-             A.kn, ck_ready};
-    S.ck_path = ck_path;
-    S.tsh = tsh;
-    // element builds (hashed paths, few per segment): the leading 24 composite bits suffice
-    if (A.el && !A.kn && sb <= 18 && (segmented ? n / A.nseg : n) <= (1ull << (19 - (segmented ? sb : 0))))
-      S.rs_lo = 40;
-    S.speculate = spec;
-    S.u = T.u;
-    S.depth0 = A.depth0;
-    sort_dedup(c, S);
-    m = S.m;
-    sidx = S.sidx;
-    skey = S.skey;
-    sseg = S.sseg;
-    fallback = S.fallback;
-    T.sck = S.sck;  // non-null: no sorted keys materialised (trie_ops.h sorted_key)
-    T.ck_sb = S.sck ? sb : 0;
-    ties_u = S.ties_u;
-    all_u = S.all_u;
-  }
-  const bool ties = fallback;
+  S.K32 = K32;
+  S.ctr = T.ctr;
+  S.kn = A.kn;
+  S.ck_ready = ck_ready;
+  S.ck_path = ck_path;
+  S.tsh = tsh;
+  // element builds (hashed paths, few per segment): the leading 24 composite bits suffice
+  if (A.el && !A.kn && sb <= 18 && (segmented ? n / A.nseg : n) <= (1ull << (19 - (segmented ? sb : 0))))
+    S.rs_lo = 40;
+  S.speculate = spec;
+  S.u = T.u;
+  S.depth0 = A.depth0;
+  sort_dedup(c, S);
+  const uint64_t m = S.m;
+  uint32_t* const sidx = S.sidx;
+  const bool ties = S.fallback, ties_u = S.ties_u, all_u = S.all_u;
+  T.sck = S.sck;  // non-null: no sorted keys materialised (trie_ops.h sorted_key)
+  T.ck_sb = S.sck ? sb : 0;
   T.m = m;
-  T.skey = skey;
+  T.skey = S.skey;
   T.sidx = sidx;
-  T.sseg = sseg;
+  T.sseg = S.sseg;
   if (early) {  // the leaves read their spans in input order; long ones through sidx
     T.svoff = nullptr;
     T.svlen = nullptr;
@@ -2580,16 +2527,17 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   }
   if (A.el) {  // element build: the element properties in sorted order (the leaf topology reads them)
     ElemArgs& E = *A.el;
-    E.out->ensure(carve_size({m, m * 32, m, m, m * 32, m, m * 32, m * 4}));
-    Carver ce{(char*)E.out->p, 0, E.out->cap};
-    uint8_t* edb = ce.take<uint8_t>(m);
-    uint64_t* ebref = ce.take<uint64_t>(m * 4);
-    uint8_t* ebrl = ce.take<uint8_t>(m);
-    uint8_t* eoldd = ce.take<uint8_t>(m);
-    uint64_t* ecref = ce.take<uint64_t>(m * 4);
-    uint8_t* ecrl = ce.take<uint8_t>(m);
-    T.lf_ref = ce.take<uint64_t>(m * 4);
-    T.lf_rlen = ce.take<uint32_t>(m);
+    Layout Le;
+    uint8_t *edb, *ebrl, *eoldd, *ecrl;
+    uint64_t *ebref, *ecref;
+    Le.add(edb, m);
+    Le.add(ebref, m * 4);
+    Le.add_all(m, ebrl, eoldd);
+    Le.add(ecref, m * 4);
+    Le.add(ecrl, m);
+    Le.add(T.lf_ref, m * 4);
+    Le.add(T.lf_rlen, m);
+    place(*E.out, Le);
     hipLaunchKernelGGL(k_el_gather3, GRID(m, BS), dim3(BS), 0, st, T, E.db, E.bref, E.brl, edb, ebref, ebrl, E.oldd,
                        E.cref, E.crl, eoldd, ecref, ecrl);
     LAUNCH_CHECK();
@@ -2747,9 +2695,9 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
       hipLaunchKernelGGL(k_rep_popc, topo_grid(rb_words), dim3(BS), 0, st, (const uint32_t*)T.rep_bits, rb_words,
                          rb_pref);
       LAUNCH_CHECK();
-      scan_exclusive<uint32_t>(rb_pref, rb_pref, rb_words, Bp, scan_scratch, st);
+      scan_exclusive<uint32_t>(rb_pref, rb_pref, rb_words, Bp, S.scan_scratch, st);
     } else {
-      scan_exclusive<uint32_t>(T.isrep_bid, T.isrep_bid, nb, Bp, scan_scratch, st);
+      scan_exclusive<uint32_t>(T.isrep_bid, T.isrep_bid, nb, Bp, S.scan_scratch, st);
     }
     // branch tables in key-order ids first (k_branch_topo writes them, thread per boundary)
     Topo TJ = T;
@@ -2770,7 +2718,7 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
     LAUNCH_CHECK();
     // (a small table: one block scans the bound's entries, those past the device's count unread later)
     const uint64_t nbt = (uint64_t)NBUCKET * nblk;
-    scan_exclusive<uint32_t>(bcnt, bcnt, nbt, (uint32_t*)nullptr, scan_scratch, st, true,
+    scan_exclusive<uint32_t>(bcnt, bcnt, nbt, (uint32_t*)nullptr, S.scan_scratch, st, true,
                              nbt > SCAN_SMALL_MAX ? (const uint32_t*)ncnt : nullptr);
     hipLaunchKernelGGL(k_level_scatter, dim3(nblk), dim3(BS), 0, st, TJ, (const uint32_t*)Bp,
                        (const uint32_t*)bcnt, order);
@@ -2790,7 +2738,7 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
     }
     // child record bases: the first B entries only (B from the device; no clearing of the
     // entries past it, and a third of the 100M-entry scan's traffic beside the leaf kernel)
-    scan_exclusive<uint32_t>(T.br_k, T.br_cbase, nb, (uint32_t*)(ctr + CTR_C), scan_scratch, st, true,
+    scan_exclusive<uint32_t>(T.br_k, T.br_cbase, nb, (uint32_t*)(ctr + CTR_C), S.scan_scratch, st, true,
                              (const uint32_t*)Bp);
   }
   if (early && !lpos) {  // the leaves' slots, while they are still being hashed
@@ -2807,7 +2755,7 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   // histogram and the level bounds are carved back to back, one copy.  Early builds take it
   // while the leaf kernel still runs (the child records are carved and cleared beside it) and
   // read the leaves' own counters (long and inline leaves) with a second, short one
-  const size_t tcopy = (size_t)((char*)(lb + 65) - (char*)ctr);
+  const size_t tcopy = o_lb - o_ctr + 65 * 4;
   if (tcopy > 16384) throw KhError{KH_EINTERNAL, "counter block exceeds the pinned staging"};
   HIPCHK(hipMemcpyAsync(c->h_pinned, ctr, tcopy, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -2827,7 +2775,7 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
                                     : "topology invariant violated (group chain > 15)"};
   }
   std::vector<uint32_t> lbh(65, 0);
-  memcpy(lbh.data(), (const char*)hc + ((char*)lb - (char*)ctr), 65 * 4);
+  memcpy(lbh.data(), (const char*)hc + (o_lb - o_ctr), 65 * 4);
   if (nb == 0) std::fill(lbh.begin(), lbh.end(), 0u);
 
   // ---- phase-2 workspace: child records + node arena
@@ -2836,16 +2784,17 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   const bool lmsgs = A.emit || A.kn || A.el;
   const uint64_t lmsg_words = lmsgs ? (uint64_t)LEAF_WORDS * m : 0;
   const uint64_t bmsg_words = A.emit ? (uint64_t)BR_WORDS * B : 0, xmsg_words = A.emit ? (uint64_t)EXT_WORDS * B : 0;
-  c->ws2.ensure(carve_size({C * 32, C * 2, lmsg_words * 8, bmsg_words * 8, xmsg_words * 8, lpos ? C * 4 : 0}));
-  Carver cv2{(char*)c->ws2.p, 0, c->ws2.cap};
-  T.cref = cv2.take<uint64_t>(C * 4);
-  T.cmeta = cv2.take<uint16_t>(C);
-  T.lmsg = lmsgs ? cv2.take<uint64_t>(lmsg_words) : nullptr;
+  Layout L2;
+  L2.add(T.cref, C * 4);
+  L2.add(T.cmeta, C);
+  L2.add(T.lmsg, lmsg_words, lmsgs);
+  L2.add(T.cend, C, lpos);
+  L2.add(T.bmsg, bmsg_words, A.emit);
+  L2.add(T.xmsg, xmsg_words, A.emit);
+  place(c->ws2, L2);
   T.lstride = m;
-  if (lpos) {  // a record without CM_BR is a leaf child's: the metas start at zero
-    T.cend = cv2.take<uint32_t>(C);
-    HIPCHK(hipMemsetAsync(T.cmeta, 0, C * 2, st));
-  }
+  // a record without CM_BR is a leaf child's: the metas start at zero
+  if (lpos) HIPCHK(hipMemsetAsync(T.cmeta, 0, C * 2, st));
   if (early) {  // the leaves' counters: their long-leaf bytes, long and inline leaves
     HIPCHK(hipStreamWaitEvent(st, c->ev[10], 0));
     HIPCHK(hipMemcpyAsync(c->h_pinned, ctr, (size_t)CTR_N * CTR_SHARDS * 8, hipMemcpyDeviceToHost, st));
@@ -2862,18 +2811,16 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   }
   c->ws_arena.ensure(lf_bytes + 64);
   T.arena = (uint8_t*)c->ws_arena.p;  // long leaves
-  T.bmsg = A.emit ? cv2.take<uint64_t>(bmsg_words) : nullptr;
-  T.xmsg = A.emit ? cv2.take<uint64_t>(xmsg_words) : nullptr;
   T.lb = lb;
   T.wlist = tlist_a;  // (the tile topology's list, free again: >= B entries)
   if (A.el) {  // element build: every capped reference kept for the forest's records
     ElemArgs& E = *A.el;
-    E.outb->ensure(carve_size({B * 32, B * 4, B * 32, B * 4}));
-    Carver ce{(char*)E.outb->p, 0, E.outb->cap};
-    T.br_ref = ce.take<uint64_t>(B * 4);
-    T.br_rlen = ce.take<uint32_t>(B);
-    T.ex_ref = ce.take<uint64_t>(B * 4);
-    T.ex_rlen = ce.take<uint32_t>(B);
+    Layout Le;
+    Le.add(T.br_ref, B * 4);
+    Le.add(T.br_rlen, B);
+    Le.add(T.ex_ref, B * 4);
+    Le.add(T.ex_rlen, B);
+    place(*E.outb, Le);
     T.emit_sel = nullptr;  // the forest sets its write-back selection after the build
   }
   if (!early && stage_ev) HIPCHK(hipEventRecord(c->ev[3], st));
@@ -2899,23 +2846,25 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
     // lists the re-encoded ones (counter CTR_LIST, zero since the build's counter memset),
     // which k_leaf_hash_list hashes in full waves
     unsigned long long* nlist = A.el ? T.ctr + CTR_LIST : nullptr;
-    uint32_t* list = nullptr;
+    uint32_t *list = nullptr, *late = nullptr;
     // late values still to come: the other leaves first, the late ones after them (when they are
     // on the device already, one pass: a second costs ~60 us of latency)
     const bool split = A.el && T.el_late && !(A.late_ready && A.late_ready());
     if (A.el) {
-      c->ws_list.ensure(carve_size({m * 4, split ? m * 4 : 0}));
-      list = (uint32_t*)c->ws_list.p;
+      Layout Ll;
+      Ll.add(list, m);
+      Ll.add(late, m, split);
+      place(c->ws_list, Ll);
     }
     const uint64_t lblocks = std::max<uint64_t>(std::min<uint64_t>((uint64_t)c->n_cu * 4, (m + BS - 1) / BS), 1);
     if (split) {
-      hipLaunchKernelGGL(k_leaf_prep, GRID(m, BS), dim3(BS), 0, st, T, list, nlist, 1, list + m, T.ctr + CTR_LIST2);
+      hipLaunchKernelGGL(k_leaf_prep, GRID(m, BS), dim3(BS), 0, st, T, list, nlist, 1, late, T.ctr + CTR_LIST2);
       hipLaunchKernelGGL(k_leaf_hash_list, dim3((unsigned)lblocks), dim3(BS), 0, st, T, (const uint32_t*)list,
                          (const unsigned long long*)nlist);
       LAUNCH_CHECK();
     }
     if (A.before_leaves) A.before_leaves();  // (a block commit's account values arrive here)
-    hipLaunchKernelGGL(k_leaf_prep, GRID(m, BS), dim3(BS), 0, st, T, list, nlist, split ? 2 : 0, list + m,
+    hipLaunchKernelGGL(k_leaf_prep, GRID(m, BS), dim3(BS), 0, st, T, list, nlist, split ? 2 : 0, late,
                        T.ctr + CTR_LIST2);
     LAUNCH_CHECK();
     if (split) {  // (the late leaves were hashed by the pass itself)
@@ -2996,9 +2945,6 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
   // through pinned staging: device-to-host copies into pageable memory pin its pages on
   // every call (measured: 20-30 ms per build for 100k roots, scripts/storage_wall_probe.py).
   // The results and the counters are carved back to back: one copy.
-  const size_t o_len = (size_t)((char*)T.res_len - (char*)T.res_hash);
-  const size_t o_inl = (size_t)((char*)T.res_inl - (char*)T.res_hash);
-  const size_t o_ctr = (size_t)((char*)ctr - (char*)T.res_hash);
   uint8_t* hr = pinned_stage(c, o_ctr + CTR_N * CTR_SHARDS * 8);
   HIPCHK(hipMemcpyAsync(hr, T.res_hash, o_ctr + CTR_N * CTR_SHARDS * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -4280,23 +4226,22 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   HIPCHK(hipEventRecord(c->ev[6], st));
   // ---- 1. op keys (the trie's key encoder), trie ids, sort by (trie, key), last op wins
   const bool segd = h->forest;
-  std::vector<size_t> sz = {nops * 32, nops * 4, nops * 8, nops * 8, nops * 4, nops * 4, nops * 32, nops * 4,
-                            radix_scratch_bytes(nops), scan_scratch_bytes(nops + 1, 8), CTR_N * 8,
-                            nops, nops * 4, nops * 4, nops * 4, (nops + 1) * 8, nops * 8, nops * 4};
-  h->ws.ensure(carve_size(sz));
-  Carver cv{(char*)h->ws.p, 0, h->ws.cap};
-  uint64_t* K = cv.take<uint64_t>(nops * 4);
-  uint32_t* Tid = cv.take<uint32_t>(nops);
+  Layout L;
+  uint64_t *K, *uoff, *ulen;
+  uint32_t *Tid, *tflag, *tpos, *isup, *ur;
+  uint8_t* kind;
   SortIO S{};
+  L.add(K, nops * 4);
+  L.add(Tid, nops);
+  S.declare(L, nops, nops * 4, true, nops, nops + 1, CTR_N);
+  L.add_all(nops, kind, tflag, tpos, isup);
+  L.add(uoff, nops + 1);
+  L.add_all(nops, ulen, ur);
+  place(h->ws, L);
   S.K32 = K;
   S.n = nops;
-  S.ck0 = cv.take<uint64_t>(nops);
-  S.ck1 = cv.take<uint64_t>(nops);
-  S.idx0 = cv.take<uint32_t>(nops);
-  S.idx1 = cv.take<uint32_t>(nops);
-  S.skey = cv.take<uint64_t>(nops * 4);
-  uint32_t* sseg = cv.take<uint32_t>(nops);
-  S.sseg = segd ? sseg : nullptr;
+  uint32_t* const sseg = S.sseg;  // (an unsegmented sort has none; the trie ids of the ops below)
+  if (!segd) S.sseg = nullptr;
   S.seg = segd ? Tid : nullptr;
   // the trie ids' bits: a hint from the ids committed before (two bits of headroom; the sort is
   // redone with 32 if an id needs more), so the sorted 32-bit prefix holds key bits too and
@@ -4311,18 +4256,8 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   if ((h->flags & KH_HASH_KEYS) && S.sb <= 18 && nops <= (segd ? (1ull << 17) : (1ull << 19)) && h->lo24_off == 0)
     S.rs_lo = 40;
   if (h->lo24_off) --h->lo24_off;
-  S.rs_scratch = cv.take<char>(radix_scratch_bytes(nops));
-  S.scan_scratch = cv.take<char>(scan_scratch_bytes(nops + 1, 8));
-  S.ctr = cv.take<unsigned long long>(CTR_N);
   const bool defer = (bool)F.before_values;
   S.chk = defer ? nullptr : F.chk;
-  uint8_t* kind = cv.take<uint8_t>(nops);
-  uint32_t* tflag = cv.take<uint32_t>(nops);
-  uint32_t* tpos = cv.take<uint32_t>(nops);
-  uint32_t* isup = cv.take<uint32_t>(nops);
-  uint64_t* uoff = cv.take<uint64_t>(nops + 1);
-  uint64_t* ulen = cv.take<uint64_t>(nops);
-  uint32_t* ur = cv.take<uint32_t>(nops);
   if (segd && ((F.nup && !F.up_trie) || (F.ndel && !F.del_trie))) throw KhError{KH_EINVAL, "forest ops need trie ids"};
   // the op keys (unless hashed above) and trie ids, upserts then deletes: one launch
   bool copy_keys = !(h->flags & KH_HASH_KEYS);
@@ -4361,11 +4296,14 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   // the descent's touched list and the commit's flags (fctr, zeroed by k_f_prep): [0] touched
   // count, [1] replaced leaves, [2] anchor-map error, [3] refusal / map insert error,
   // [4] fresh map slots, [5] element count, [6] value-only branches made, [7] the hashed ones
-  h->tlb.ensure(carve_size({nd * 70 * 4 + 64, 64, nd + 64}));
-  Carver c3{(char*)h->tlb.p, 0, h->tlb.cap};
-  uint32_t* tlist = c3.take<uint32_t>(nd * 70 + 16);
-  unsigned long long* fctr = c3.take<unsigned long long>(8);
-  uint8_t* vbf = c3.take<uint8_t>(nd + 64);  // ops that make a value-only branch
+  Layout L3;
+  uint32_t* tlist;
+  unsigned long long* fctr;
+  uint8_t* vbf;  // ops that make a value-only branch
+  L3.add(tlist, nd * 70 + 16);
+  L3.add(fctr, 8);
+  L3.add(vbf, nd + 64);
+  place(h->tlb, L3);
   // kinds, the distinct tries of the batch (sorted: the segments of the element build), and
   // the upserts' ranks and value offsets (their values go to the heap)
   hipLaunchKernelGGL(k_f_prep, GRID(nd, BS), dim3(BS), 0, st, (const uint32_t*)S.sidx, nd, F.nup, segd, otrie,
@@ -4390,11 +4328,14 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   // ---- trie list; upsert values into the heap (appended past heap_n, which moves only once
   // the commit is accepted): uoff is the exclusive scan of their lengths over the sorted
   // ops, uo the same offsets by upsert rank (uo[nups] = total)
-  h->tbuf.ensure(carve_size({(uint64_t)nt * 4, (uint64_t)nt * 32, 64}));
-  Carver ct{(char*)h->tbuf.p, 0, h->tbuf.cap};
-  uint32_t* tries = ct.take<uint32_t>(nt);
-  uint64_t* roots = ct.take<uint64_t>((uint64_t)nt * 4);
-  unsigned long long* tail = ct.take<unsigned long long>(8);  // k_f_roots: the final flags
+  Layout Lt;
+  uint32_t* tries;
+  uint64_t* roots;
+  unsigned long long* tail;  // k_f_roots: the final flags
+  Lt.add(tries, nt);
+  const size_t o_roots = Lt.add(roots, (uint64_t)nt * 4);
+  const size_t o_tail = Lt.add(tail, 8);
+  place(h->tbuf, Lt);
   h->d_tries = tries;
   h->d_roots = roots;
   regrow(h->heap, h->heap_n, h->heap_n + ubytes + 64, st);
@@ -4413,22 +4354,16 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   Elems E{};
   auto carve_elems = [&](uint64_t ntl_cap) {
     const uint64_t ecap = (uint64_t)nups + 16 * ntl_cap + nt + 16;
-    h->ebuf.ensure(
-        carve_size({ecap * 32, ecap * 4, ecap, ecap * 32, ecap, ecap * 8, ecap * 4, ecap * 4, ecap, ecap * 32, ecap, ecap, 64}));
-    Carver ce{(char*)h->ebuf.p, 0, h->ebuf.cap};
+    Layout Le;
     E = Elems{};
-    E.key = ce.take<uint64_t>(ecap * 4);
-    E.seg = ce.take<uint32_t>(ecap);
-    E.db = ce.take<uint8_t>(ecap);
-    E.bref = ce.take<uint64_t>(ecap * 4);
-    E.brl = ce.take<uint8_t>(ecap);
-    E.vo = ce.take<uint64_t>(ecap);
-    E.vl = ce.take<uint32_t>(ecap);
-    E.src = ce.take<uint32_t>(ecap);
-    E.oldd = ce.take<uint8_t>(ecap);
-    E.cref = ce.take<uint64_t>(ecap * 4);
-    E.crl = ce.take<uint8_t>(ecap);
-    E.late = ce.take<uint8_t>(ecap);
+    Le.add(E.key, ecap * 4);
+    Le.add_all(ecap, E.seg, E.db);
+    Le.add(E.bref, ecap * 4);
+    Le.add_all(ecap, E.brl, E.vo, E.vl, E.src, E.oldd);
+    Le.add(E.cref, ecap * 4);
+    Le.add_all(ecap, E.crl, E.late);
+    Le.pad(64);
+    place(h->ebuf, Le);
     E.n = fctr + 5;
     E.cap = ecap;
     return ecap;
@@ -4553,7 +4488,6 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   // after them, trie_settle reads their flags): configs[2]'s account phase ends 0.1 ms sooner
   const bool rebuild = ne && 2 * (h->mused + B + m + 1024) > h->mcap;
   const bool lazy = ne && !keep_em && !rebuild;
-  const size_t o_roots = (size_t)((char*)roots - (char*)tries), o_tail = (size_t)((char*)tail - (char*)tries);
   uint8_t* hs = nullptr;
   if (ne && (lazy || F.after_roots)) {  // the roots now (k_f_roots runs again with the final flags below)
     hipLaunchKernelGGL(k_f_roots, GRID(nt, BS), dim3(BS), 0, st, (const uint64_t*)c->T.res_hash,
@@ -4607,16 +4541,15 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     h->jmap_n += ndel_log + nins_log;
   };
   if (ne) {
-    h->selb.ensure(carve_size({m + 2 * B, m * 4, m * 4, m * 4, m * 4, m, scan_scratch_bytes(m + 1, 4), 64}));
-    Carver cs{(char*)h->selb.p, 0, h->selb.cap};
-    sel = cs.take<uint8_t>(m + 2 * B);
-    uint8_t* rein = cs.take<uint8_t>(m);
-    isnew = cs.take<uint32_t>(m);
-    nrank = cs.take<uint32_t>(m);
-    eid = cs.take<uint32_t>(m);
-    esrc = cs.take<uint32_t>(m);
-    void* sscr = cs.take<char>(scan_scratch_bytes(m + 1, 4));
-    uint32_t* tot = cs.take<uint32_t>(8);
+    Layout Ls;
+    uint8_t* rein;
+    void* sscr;
+    uint32_t* tot;
+    Ls.add(sel, m + 2 * B);
+    Ls.add_all(m, rein, isnew, nrank, eid, esrc);
+    Ls.add(sscr, scan_scratch_bytes(m + 1, 4));
+    Ls.add(tot, 8);
+    place(h->selb, Ls);
     Topo T = c->T;
     if (B)
       hipLaunchKernelGGL(k_f_branch_recs, GRID(B, BS), dim3(BS), 0, st, T, (const uint32_t*)(T.ctr + CTR_B),
@@ -5311,10 +5244,12 @@ static int emit_nodes_dev(kh_ctx* c, DevBuf& out, uint64_t* n_nodes, uint64_t* r
   uint64_t Q = T.m + 2 * B;
   // node counts and positions are scanned as uint32
   if (Q >= (1ULL << 32)) throw KhError{KH_EINVAL, "node set too large to emit in one call (>= 2^32 candidates)"};
-  c->ws3.ensure(carve_size({Q * 4, Q * 8, Q * 8 + 64}));
-  Carver c3{(char*)c->ws3.p, 0, c->ws3.cap};
-  uint32_t* flag = c3.take<uint32_t>(Q);
-  uint64_t* bytes = c3.take<uint64_t>(Q);
+  Layout L3;
+  uint32_t* flag;
+  uint64_t* bytes;
+  L3.add_all(Q, flag, bytes);
+  L3.pad(Q * 8 + 64);
+  place(c->ws3, L3);
   hipStream_t st = c->st;
   hipLaunchKernelGGL(k_emit_sizes, GRID(Q, BS), dim3(BS), 0, st, T, B, flag, bytes);
   LAUNCH_CHECK();
@@ -5476,22 +5411,25 @@ static void partition_impl(kh_ctx* c, void* vals_done, const uint8_t* d_addr, ui
     hipStream_t st = c->st;
     const uint32_t ntile = (uint32_t)((n + PT_TILE - 1) / PT_TILE);
     const uint64_t nh = (uint64_t)nparts * ntile;
-    c->ws3.ensure(carve_size({nh * 4, n * 4, n * 8, scan_scratch_bytes(std::max<uint64_t>(n, nh), 8), 40 * 8,
-                              d_addr ? n * 32 : 0, nh * 8, d_addr ? n + 16 : 0}));
-    Carver cv{(char*)c->ws3.p, 0, c->ws3.cap};
-    uint32_t* hist = cv.take<uint32_t>(nh);
-    uint32_t* pos = cv.take<uint32_t>(n);
-    uint64_t* ooff = cv.take<uint64_t>(n);
-    void* sc = cv.take<char>(scan_scratch_bytes(std::max<uint64_t>(n, nh), 8));
-    unsigned long long* tot = cv.take<unsigned long long>(40);  // counts | bytes | byte total
+    // the place pass sums the tiles' value bytes per owner (hbytes): the counts and bytes go back
+    // to the host before the scan of the placed lengths (that scan, and with vals_done the value
+    // copy, run after the return)
+    Layout L;
+    uint32_t *hist, *pos;
+    uint64_t *ooff, *hk;
+    void* sc;
+    unsigned long long *tot, *hbytes;  // tot: counts | bytes | byte total
+    uint8_t* ob;
+    L.add(hist, nh);
+    L.add_all(n, pos, ooff);
+    L.add(sc, scan_scratch_bytes(std::max<uint64_t>(n, nh), 8));
+    L.add(tot, 40);
+    L.add(hbytes, nh);
+    L.add(hk, n * 4, d_addr != nullptr);
+    L.add(ob, n + 16, d_addr != nullptr);
+    place(c->ws3, L);
     const uint64_t* K = (const uint64_t*)d_keys32;
-    // the place pass sums the tiles' value bytes per owner: the counts and bytes go back to the
-    // host before the scan of the placed lengths (that scan, and with vals_done the value copy,
-    // run after the return)
-    unsigned long long* hbytes = cv.take<unsigned long long>(nh);
     if (d_addr) {  // hashed here, each owner written as a byte that the count pass reads
-      uint64_t* hk = cv.take<uint64_t>(n * 4);
-      uint8_t* ob = cv.take<uint8_t>(n + 16);
       if (klen <= 135)
         hipLaunchKernelGGL(k_hash_keys_owner_s, GRID(n, BS), dim3(BS), 0, st, d_addr, klen, n, hk, nparts, ob);
       else
@@ -5612,10 +5550,14 @@ int kh_dev_synth_storage(kh_ctx* c, uint32_t cfg, uint64_t t0, uint64_t nt, uint
     *n_slots = n;
     const bool write = d_keys != nullptr;
     if (write && (!d_vals || !d_voff || !d_seg)) throw KhError{KH_EINVAL, "null output"};
-    c->ws3.ensure(carve_size({n * 4 + 64, (n + 1) * 8 + 64}));
-    Carver cv{(char*)c->ws3.p, 0, c->ws3.cap};
-    uint32_t* seg = write ? d_seg : cv.take<uint32_t>(n + 16);
-    uint64_t* vo = write ? d_voff : cv.take<uint64_t>(n + 1);
+    Layout L;  // (a counting call's segment ids and value offsets)
+    uint32_t* wseg;
+    uint64_t* wvo;
+    L.add(wseg, n + 16);
+    L.add(wvo, n + 1 + 8);
+    place(c->ws3, L);
+    uint32_t* seg = write ? d_seg : wseg;
+    uint64_t* vo = write ? d_voff : wvo;
     if (n) {
       hipLaunchKernelGGL(k_seg_ids, GRID(n, BS), dim3(BS), 0, st, (const uint64_t*)d_seg_off, nt, n, seg);
       LAUNCH_CHECK();
@@ -5684,10 +5626,12 @@ static int verify_nodes_impl(const uint8_t* data, const uint64_t* off, uint64_t 
   c->in_vals.ensure(vbytes + 64);
   c->in_voff.ensure((n + 1) * 8 + 64);
   const uint64_t nr = nreq ? nreq : 1;
-  c->in_keys.ensure(carve_size({32 * nr + 32, nr + 1}));
-  Carver ci{(char*)c->in_keys.p, 0, c->in_keys.cap};
-  uint64_t* dreq = ci.take<uint64_t>(4 * nr + 4);
-  uint8_t* dkind = ci.take<uint8_t>(nr + 1);
+  Layout Li;
+  uint64_t* dreq;
+  uint8_t* dkind;
+  Li.add(dreq, 4 * nr + 4);
+  Li.add(dkind, nr + 1);
+  place(c->in_keys, Li);
   if (vbytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, data + v0, vbytes, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
   if (nreq) {
@@ -5695,13 +5639,10 @@ static int verify_nodes_impl(const uint8_t* data, const uint64_t* off, uint64_t 
     HIPCHK(hipMemcpyAsync(dkind, req_kind, nreq, hipMemcpyHostToDevice, st));
   }
   // the requests in key order, one per distinct hash (sort_dedup: the last duplicate kept)
-  c->ws1.ensure(carve_size({nr * 8, nr * 8, nr * 4, nr * 4, nr * 32, radix_scratch_bytes(nr),
-                            scan_scratch_bytes(nr, 8), CTR_N * 8}));
-  Carver cs{(char*)c->ws1.p, 0, c->ws1.cap};
-  SortIO S{(const uint64_t*)dreq, nullptr, 0, nreq, cs.take<uint64_t>(nr), cs.take<uint64_t>(nr),
-           cs.take<uint32_t>(nr), cs.take<uint32_t>(nr), cs.take<uint64_t>(nr * 4), nullptr,
-           cs.take<char>(radix_scratch_bytes(nr)), cs.take<char>(scan_scratch_bytes(nr, 8)),
-           cs.take<unsigned long long>(CTR_N), nullptr, false};
+  Layout Ls;
+  SortIO S{dreq, nullptr, 0, nreq};
+  S.declare(Ls, nr, nr * 4, false, nr, nr, CTR_N);
+  place(c->ws1, Ls);
   uint64_t m = 0;
   const uint64_t* skey = dreq;
   const uint32_t* sidx = nullptr;
@@ -5719,20 +5660,22 @@ static int verify_nodes_impl(const uint8_t* data, const uint64_t* off, uint64_t 
     }
   }
   // per value: hash, match, decode (16-slot rows), then the children packed
-  c->out_emit.ensure(carve_size({32 * n, 8 * n, n, 4 * n, 512 * n, 16 * n, 8 * (n + 1), scan_scratch_bytes(n + 1, 8),
-                                 32 * 16 * n, 16 * n, 64}));
-  Carver co{(char*)c->out_emit.p, 0, c->out_emit.cap};
-  uint64_t* dh = co.take<uint64_t>(4 * n);
-  int64_t* dm = co.take<int64_t>(n);
-  uint8_t* ds = co.take<uint8_t>(n);
-  uint32_t* dn = co.take<uint32_t>(n);
-  uint8_t* dc = co.take<uint8_t>(512 * n);
-  uint8_t* dk = co.take<uint8_t>(16 * n);
-  uint64_t* coff = co.take<uint64_t>(n + 1);
-  void* sscr = co.take<char>(scan_scratch_bytes(n + 1, 8));
-  uint8_t* pc = co.take<uint8_t>(32 * 16 * n);
-  uint8_t* pk = co.take<uint8_t>(16 * n);
-  uint64_t* tot = co.take<uint64_t>(8);
+  Layout Lo;
+  uint64_t *dh, *coff, *tot;
+  int64_t* dm;
+  uint8_t *ds, *dc, *dk, *pc, *pk;
+  uint32_t* dn;
+  void* sscr;
+  Lo.add(dh, 4 * n);
+  Lo.add_all(n, dm, ds, dn);
+  Lo.add(dc, 512 * n);
+  Lo.add(dk, 16 * n);
+  Lo.add(coff, n + 1);
+  Lo.add(sscr, scan_scratch_bytes(n + 1, 8));
+  Lo.add(pc, 32 * 16 * n);
+  Lo.add(pk, 16 * n);
+  Lo.add(tot, 8);
+  place(c->out_emit, Lo);
   hipLaunchKernelGGL(k_verify_nodes, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)c->in_vals.p,
                      (const uint64_t*)c->in_voff.p, n, skey, (const uint8_t*)dkind, sidx, m, dh, dm, ds, dn, dc, dk);
   LAUNCH_CHECK();
@@ -5811,17 +5754,16 @@ int kh_verify_nodes_packed(const uint8_t* data, const uint64_t* off, uint64_t n,
 }
 
 static OItems oitems_carve(DevBuf& b, uint64_t cap) {
-  b.ensure(carve_size({cap * 32, cap, cap, cap * 32, cap, cap * 32, cap, 64}));
-  Carver cv{(char*)b.p, 0, b.cap};
+  Layout L;
   OItems I{};
-  I.pre = cv.take<uint64_t>(cap * 4);
-  I.a = cv.take<uint8_t>(cap);
-  I.d = cv.take<uint8_t>(cap);
-  I.ref = cv.take<uint64_t>(cap * 4);
-  I.rl = cv.take<uint8_t>(cap);
-  I.pref = cv.take<uint64_t>(cap * 4);
-  I.prl = cv.take<uint8_t>(cap);
-  I.n = cv.take<unsigned long long>(8);
+  L.add(I.pre, cap * 4);
+  L.add_all(cap, I.a, I.d);
+  L.add(I.ref, cap * 4);
+  L.add(I.rl, cap);
+  L.add(I.pref, cap * 4);
+  L.add(I.prl, cap);
+  L.add(I.n, 8);
+  place(b, L);
   I.cap = cap;
   return I;
 }
@@ -5835,24 +5777,18 @@ static void trie_open_nodes(kh_trie* h, const uint8_t* root32, const uint8_t* d_
   if (memcmp(root32, EMPTY_TRIE_HASH, 32) == 0) return;  // MerklePatriciaTrie.scala:60-66
   if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "node store too large"};
   // the store, keyed by kec256 of each encoding (content addressed)
-  std::vector<size_t> sz = {n * 32 + 32, n * 8, n * 8, n * 4, n * 4, n * 32 + 32, radix_scratch_bytes(n + 1),
-                            scan_scratch_bytes(n + 1, 8), CTR_N * 8, 64, 64};
-  h->ws.ensure(carve_size(sz));
-  Carver cv{(char*)h->ws.p, 0, h->ws.cap};
-  uint64_t* hs = cv.take<uint64_t>(n * 4 + 4);
+  Layout L;
+  uint64_t* hs;
   SortIO S{};
+  unsigned long long* oc;  // records, heap bytes, leaves, error
+  uint8_t* dmiss;
+  L.add(hs, n * 4 + 4);
+  S.declare(L, n, n * 4 + 4, false, n + 1, n + 1, CTR_N);
+  L.add(oc, 8);
+  L.add(dmiss, 64);
+  place(h->ws, L);
   S.K32 = hs;
   S.n = n;
-  S.ck0 = cv.take<uint64_t>(n);
-  S.ck1 = cv.take<uint64_t>(n);
-  S.idx0 = cv.take<uint32_t>(n);
-  S.idx1 = cv.take<uint32_t>(n);
-  S.skey = cv.take<uint64_t>(n * 4 + 4);
-  S.rs_scratch = cv.take<char>(radix_scratch_bytes(n + 1));
-  S.scan_scratch = cv.take<char>(scan_scratch_bytes(n + 1, 8));
-  S.ctr = cv.take<unsigned long long>(CTR_N);
-  unsigned long long* oc = cv.take<unsigned long long>(8);  // records, heap bytes, leaves, error
-  uint8_t* dmiss = cv.take<uint8_t>(64);
   HIPCHK(hipMemsetAsync(S.ctr, 0, CTR_N * 8, st));
   HIPCHK(hipMemsetAsync(oc, 0, 64, st));
   uint64_t total = 0;
@@ -6517,13 +6453,16 @@ static int trie_get(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, u
   if (!(h->flags & KH_HASH_KEYS) && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
   if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
   if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
-  h->gbuf.ensure(carve_size({n * 32 + 64, n * 4, (n + 1) * 8, scan_scratch_bytes(n + 1, 8), 64}));
-  Carver cv{(char*)h->gbuf.p, 0, h->gbuf.cap};
-  uint64_t* K = cv.take<uint64_t>(n * 4 + 8);
-  uint32_t* rec = cv.take<uint32_t>(n);
-  uint64_t* len = cv.take<uint64_t>(n + 1);
-  char* scr = cv.take<char>(scan_scratch_bytes(n + 1, 8));
-  uint64_t* tot = cv.take<uint64_t>(8);
+  Layout L;
+  uint64_t *K, *len, *tot;
+  uint32_t* rec;
+  char* scr;
+  L.add(K, n * 4 + 8);
+  L.add(rec, n);
+  L.add(len, n + 1);
+  L.add(scr, scan_scratch_bytes(n + 1, 8));
+  L.add(tot, 8);
+  place(h->gbuf, L);
   if (n) {
     if (h->flags & KH_HASH_KEYS) {
       if (klen <= 135)
@@ -6584,15 +6523,16 @@ int kh_trie_get_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
     // staging: keys and trie ids in, found flags, offsets and values out
-    c->in_keys.ensure(carve_size({n * klen + 64, trie ? n * 4 : 0}));
-    Carver ck{(char*)c->in_keys.p, 0, c->in_keys.cap};
-    uint8_t* dk = ck.take<uint8_t>(n * klen + 64);
-    uint32_t* dt = trie ? ck.take<uint32_t>(n) : nullptr;
+    Layout Lk, Lo;
+    uint8_t *dk, *df, *dv;
+    uint32_t* dt;
+    Lk.add(dk, n * klen + 64);
+    Lk.add(dt, n, trie != nullptr);
+    place(c->in_keys, Lk);
     c->in_voff.ensure((n + 1) * 8 + 64);
-    c->out_emit.ensure(carve_size({n + 64, val_cap + 64}));
-    Carver co{(char*)c->out_emit.p, 0, c->out_emit.cap};
-    uint8_t* df = co.take<uint8_t>(n + 64);
-    uint8_t* dv = co.take<uint8_t>(val_cap + 64);
+    Lo.add(df, n + 64);
+    Lo.add(dv, val_cap + 64);
+    place(c->out_emit, Lo);
     if (n) HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
     if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, st));
     const int rc = trie_get(h, dt, dk, klen, n, dv, val_cap, (uint64_t*)c->in_voff.p, df, val_bytes);

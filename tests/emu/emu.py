@@ -26,6 +26,7 @@ def lib():
         L.emu_set_link_mode.argtypes = [ctypes.c_int]
         L.emu_set_inject.argtypes = [ctypes.c_int, ctypes.c_uint64]
         L.emu_xlane_check.argtypes = [ctypes.c_uint64, ctypes.c_int]
+        L.emu_layout_check.argtypes = []
         _lib = L
     return _lib
 

@@ -19,6 +19,7 @@
 #include "../../khipu_amd/csrc/keyorder.h"
 #include "../../khipu_amd/csrc/synth.h"
 #include "../../khipu_amd/csrc/keccak_xlane.h"
+#include "../../khipu_amd/csrc/layout.h"
 
 using namespace khst;
 
@@ -542,6 +543,96 @@ extern "C" int emu_ansv_check(uint64_t seed, int iters) {
         }
       if (ansv_right(P, b, t) != e) return 2;
     }
+  }
+  return 0;
+}
+
+// The workspace layout arithmetic (layout.h, the host code of khst.hip): known answers of the
+// bump carving it replaced, alignment, disjointness and slack of a mixed layout, writes of
+// every entry plus its slack into a heap block of exactly bytes() bytes (the sanitizer driver
+// checks their bounds), extents, and the two errors.  Returns 0 if all hold.
+struct LayoutFail {};
+[[noreturn]] static void layout_fail(const char*) { throw LayoutFail{}; }
+using TestLayout = BasicLayout<layout_fail>;
+static size_t layout_bytes_of(std::initializer_list<size_t> sizes) {
+  TestLayout L;
+  uint8_t* p;
+  for (size_t b : sizes) L.add<uint8_t>(p, b);
+  return L.bytes();
+}
+extern "C" int emu_layout_check() {
+  if (layout_bytes_of({1, 240}) != 768 || layout_bytes_of({240, 1}) != 529 || layout_bytes_of({0}) != 272 ||
+      layout_bytes_of({}) != 256)
+    return 1;
+  // a mixed layout: the four element sizes over counts 0, 1, 255, 256, 257; one entry absent
+  const size_t counts[5] = {0, 1, 255, 256, 257};
+  constexpr int NE = 21, ABSENT = 8;
+  uint8_t* p8[5];
+  uint16_t* p16[5];
+  uint32_t* p32[5];
+  uint64_t* p64[5];
+  uint32_t* gone = (uint32_t*)&p8;  // (anything but nullptr)
+  struct Span {
+    char** ptr;
+    size_t off, len;
+  } sp[NE];
+  TestLayout L;
+  int k = 0;
+  for (int i = 0; i < 5; ++i) {
+    if (k == ABSENT) sp[k++] = Span{(char**)&gone, L.add<uint32_t>(gone, 100, false), 0};
+    sp[k++] = Span{(char**)&p8[i], L.add<uint8_t>(p8[i], counts[i]), counts[i]};
+    sp[k++] = Span{(char**)&p16[i], L.add<uint16_t>(p16[i], counts[i]), counts[i] * 2};
+    sp[k++] = Span{(char**)&p32[i], L.add<uint32_t>(p32[i], counts[i]), counts[i] * 4};
+    sp[k++] = Span{(char**)&p64[i], L.add<uint64_t>(p64[i], counts[i]), counts[i] * 8};
+  }
+  if (k != NE) return 2;
+  // the extent of a run of three consecutive entries: last end - first start
+  TestLayout X;
+  uint8_t *a, *b, *c3, *d;
+  X.add<uint8_t>(a, 5);
+  const size_t x0 = X.add<uint8_t>(b, 300);
+  X.add<uint8_t>(c3, 1);
+  X.add<uint8_t>(d, 77);
+  const size_t x1 = X.end();
+  std::vector<char> xb(X.bytes());
+  X.place(xb.data(), xb.size());
+  if (x1 - x0 != (size_t)((d + 77) - b) || (char*)b != xb.data() + x0) return 3;
+  // placed into a heap block of exactly bytes() bytes; every entry and its slack written
+  const size_t total = L.bytes();
+  char* base = new char[total];
+  L.place(base, total);
+  int rc = 0;
+  if (gone != nullptr) rc = 4;
+  size_t prev_end = 0;
+  for (int i = 0; i < NE && !rc; ++i) {
+    char* q;
+    memcpy(&q, sp[i].ptr, sizeof(q));
+    if (i == ABSENT) {
+      if (q) rc = 4;
+    } else if (q != base + sp[i].off || sp[i].off % 256) {
+      rc = 5;
+    } else {
+      memset(q, 0xA5, sp[i].len + 16);
+    }
+    if (sp[i].off < prev_end || sp[i].off + sp[i].len + 16 > total) rc = rc ? rc : 6;  // disjoint, slack inside
+    prev_end = sp[i].off + sp[i].len + 16;
+  }
+  delete[] base;
+  if (rc) return rc;
+  // errors: too few bytes to place into; one entry more than the table holds
+  std::vector<char> blk(total);
+  try {
+    L.place(blk.data(), total - 1);
+    return 7;
+  } catch (LayoutFail&) {
+  }
+  TestLayout F;
+  uint8_t* e;
+  for (int i = 0; i < TestLayout::MAX_ENTRIES; ++i) F.add<uint8_t>(e, 1);
+  try {
+    F.add<uint8_t>(e, 1);
+    return 8;
+  } catch (LayoutFail&) {
   }
   return 0;
 }

@@ -30,6 +30,7 @@ int emu_build(const uint8_t* keys, const uint8_t* vals, const uint64_t* voff, ui
               uint64_t* stats_out);
 int emu_node_children(const uint8_t*, uint64_t, int, uint8_t*, uint8_t*, uint32_t*);
 int emu_ansv_check(uint64_t seed, int iters);
+int emu_layout_check();
 void emu_synth(uint32_t cfg, uint64_t first, uint64_t n, uint8_t* addr, uint8_t* vals, uint64_t* voff);
 }
 
@@ -184,6 +185,7 @@ int main() {
   segmented_synth();
   node_fuzz(7);
   CHECK(emu_ansv_check(3, 40) == 0, "ansv");
+  CHECK(emu_layout_check() == 0, "workspace layout");
   if (fails) {
     fprintf(stderr, "%d checks failed\n", fails);
     return 1;

@@ -111,6 +111,14 @@ def test_nearest_smaller_value_searches():
     assert L.emu_ansv_check(7, 150) == 0
 
 
+def test_workspace_layout_arithmetic():
+    """csrc/layout.h (the host's workspace carving): the known sizes of the bump carving it
+    replaced, 256-byte alignment, disjoint entries each with 16 bytes of slack inside bytes(),
+    an absent entry's nullptr, a run's extent, and the errors of a short buffer and a full table
+    (tests/sanitize runs the same check under ASan/UBSan)."""
+    assert E.lib().emu_layout_check() == 0
+
+
 def test_tile_topology_matches_whole_array():
     """k_topo_tile (op_tile_ansv / op_tile_chain per tile, the listed boundaries through
     op_ansv / op_chain after it) == op_ansv + op_chain on every boundary: tiles of 1..4096
