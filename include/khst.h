@@ -22,6 +22,10 @@
  *   kh_trie_roots_varkeys   generic unhashed keys of any length <= 32 B, branch values
  *   kh_list_roots           transactions / receipts roots (MptListValidator.scala:15-46)
  *   kh_trie_root_sharded    the same root computed from per-GPU top-nibble shards
+ *   kh_trie_nodes_by_hash   Blockchain.getMptNodeByHash for HostService's GetNodeData
+ *                           (khipu-eth/.../domain/Blockchain.scala:356-357, HostService.scala:103-112)
+ *   kh_trie_export_nodes    the node store of a resident trie's current version (checkpoint; the
+ *                           resume half is kh_trie_open_nodes)
  *
  * Semantics shared by every trie entry point:
  *   - input i is a put(key_i, value_i); later inputs overwrite earlier ones with the
@@ -395,7 +399,36 @@ int kh_trie_get(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, uint3
 int kh_trie_get_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
                      uint8_t* vals, uint64_t val_cap, uint64_t* voff, uint8_t* found, uint64_t* val_bytes);
 
-/* Leaves of a trie (of all tries of a forest). */
+/* ---- node export and nodes by hash: a resident handle's nodes read back out ----
+ * The checkpoint half of kh_trie_open_nodes (a state root plus its node store is the whole
+ * resumable state), for any handle: no KH_EMIT_NODES needed, no delta kept by the caller.  Both
+ * calls re-encode nodes from the records in HBM (khipu_amd/csrc/export.h), read-only on the
+ * handle: with a savepoint open they see the commits since it. */
+#define KH_EXPORT_VERIFY 0x1u
+typedef struct kh_export_cursor { uint64_t next, epoch; } kh_export_cursor;  /* zero it to start */
+
+/* Every node of the CURRENT version of a resident trie or forest that a node store needs
+ * (encoding >= 32 B, plus each trie's root node), re-encoded from the records, in chunks.
+ * trie_filter: a trie id of a forest, or KH_NO_TRIE for every trie.  Each call writes the nodes
+ * of as many consecutive records from cur->next as fit node_cap and rlp_cap (layout of
+ * kh_trie_root_nodes; off needs node_cap + 1 entries), advances *cur and sets *done when the
+ * records are exhausted.  If not even the next record fits: KH_ENOSPC with *n_nodes / *rlp_len =
+ * what it needs, cursor unchanged.  Nodes come in record order, each once; a node shared by two
+ * tries of a forest comes once per trie.
+ * A cursor from before a commit, rollback or compaction of the handle: KH_EINVAL.
+ * KH_EXPORT_VERIFY: KH_EINTERNAL if any re-hashed encoding differs from its cached reference. */
+int kh_trie_export_nodes(kh_trie* h, uint32_t trie_filter, uint32_t flags, kh_export_cursor* cur,
+                         uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap,
+                         uint64_t* off, uint64_t* n_nodes, uint64_t* rlp_len, int* done);
+
+/* getMptNodeByHash over the current version (HostService.scala:103-112, Blockchain.scala:356):
+ * found[i] = 1 and the encoding at rlp[off[i]..off[i+1]) when a node with kec256 == hashes32[32i..)
+ * is reachable from a current root; else 0 and an empty span.  n <= 4096 (KH_EINVAL above).
+ * One streaming pass over the records per 2048 hashes: no hash index is kept on the handle.
+ * KH_ENOSPC writes only *rlp_len. */
+int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8_t* found,
+                          uint8_t* rlp, uint64_t rlp_cap, uint64_t* off, uint64_t* rlp_len);
+
 /* HBM held by a resident trie or forest.  Records and the value heap are append-only between
  * compactions: a commit appends the records and values it makes and leaves the ones it
  * replaces dead (~18 MB per configs[2] block).  records / heap_bytes: in use; live_records /

@@ -854,6 +854,97 @@ JNIEXPORT jobjectArray JNICALL Java_khipu_trie_gpu_Khst_get(JNIEnv* env, jclass 
   return out;
 }
 
+/* Checkpoint: the next chunk of the current version's node store
+ * into hashes / rlp / off, the nodes NodeStorage.update(Nil, pairs) takes.  cursor: long[2], zeroed
+ * to start, advanced by the call; trieFilter: a forest's trie id or -1 (KH_NO_TRIE); flags:
+ * KH_EXPORT_VERIFY.  sizes[0] / sizes[1] = nodes / RLP bytes written, sizes[2] = 1 when the
+ * records are exhausted.  Returns the node count, or -1 when not even the next record's nodes
+ * fit the arrays (sizes[0] / sizes[1] hold what it needs: grow and call again, the cursor is
+ * unchanged).  A cursor from before a commit, rollback or compaction throws. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_exportNodes(JNIEnv* env, jclass cls, jlong handle, jint trieFilter,
+                                                            jint flags, jlongArray cursor, jbyteArray hashes,
+                                                            jbyteArray rlp, jlongArray off, jlongArray sizes) {
+  (void)cls;
+  if (len_of(env, cursor) < 2) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "exportNodes: cursor must be a long[2]");
+    return 0;
+  }
+  const uint64_t node_cap = (uint64_t)len_of(env, hashes) / 32, rlp_cap = (uint64_t)len_of(env, rlp);
+  const jsize noff = len_of(env, off);
+  const uint64_t cap = node_cap < (uint64_t)(noff > 0 ? noff - 1 : 0) ? node_cap : (uint64_t)(noff > 0 ? noff - 1 : 0);
+  jlong cw[2];
+  (*env)->GetLongArrayRegion(env, cursor, 0, 2, cw);
+  kh_export_cursor cur = {(uint64_t)cw[0], (uint64_t)cw[1]};
+  uint64_t nn = 0, nb = 0;
+  int done = 0;
+  Bufs b = {0};
+  uint8_t* hs = out_buf(env, &b, hashes, 1);
+  uint8_t* rl = out_buf(env, &b, rlp, 1);
+  uint64_t* of = out_buf(env, &b, off, 8);
+  if (bufs_failed(env, &b)) return 0;
+  const int rc = kh_trie_export_nodes(H(handle), (uint32_t)trieFilter, (uint32_t)flags, &cur, hs, cap, rl,
+                                      cap ? rlp_cap : 0, of, &nn, &nb, &done);
+  if (rc == KH_OK) {
+    put_b(env, hashes, hs, 32 * nn);
+    put_b(env, rlp, rl, nb);
+    put_l(env, off, of, nn + 1);
+    cw[0] = (jlong)cur.next;
+    cw[1] = (jlong)cur.epoch;
+    (*env)->SetLongArrayRegion(env, cursor, 0, 2, cw);
+  }
+  bufs_free(&b);
+  const jlong sz[3] = {(jlong)nn, (jlong)nb, (jlong)done};
+  put_l(env, sizes, sz, 3);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)nn;
+}
+
+/* HostService's GetNodeData (HostService.scala:103-112 -> Blockchain.getMptNodeByHash,
+ * Blockchain.scala:356-357) for a batch of 32-byte hashes (at most 4096): byte[][] with null for a
+ * hash no node of the current version has.  The encodings' size is negotiated like get's. */
+JNIEXPORT jobjectArray JNICALL Java_khipu_trie_gpu_Khst_nodesByHash(JNIEnv* env, jclass cls, jlong handle,
+                                                                   jbyteArray hashes) {
+  (void)cls;
+  const jsize n = len_of(env, hashes) / 32;
+  Bufs b = {0};
+  const uint8_t* hs = in_b(env, &b, hashes);
+  uint8_t* found = bufs_alloc(&b, (size_t)n);
+  uint64_t* off = bufs_alloc(&b, 8 * ((size_t)n + 1));
+  if (bufs_failed(env, &b)) return NULL;
+  uint64_t need = 0, cap = 0;
+  uint8_t* rl = NULL;
+  int rc = KH_ENOSPC;
+  for (int tries = 0; rc == KH_ENOSPC && tries < GET_TRIES; ++tries) { /* the first call reports the bytes needed */
+    rc = kh_trie_nodes_by_hash(H(handle), hs, (uint64_t)n, found, rl, cap, off, &need);
+    if (rc == KH_ENOSPC) {
+      free(rl);
+      cap = need + need / 8; /* headroom for a concurrent commit that grows the nodes again */
+      rl = malloc((size_t)(cap ? cap : 1));
+      if (!rl) rc = KH_ENOMEM;
+    }
+  }
+  jobjectArray out = NULL;
+  if (rc == KH_OK) {
+    jclass ba = (*env)->FindClass(env, "[B");
+    out = ba ? (*env)->NewObjectArray(env, n, ba, NULL) : NULL;
+    for (jsize i = 0; out && i < n; ++i) {
+      if (!found[i]) continue; /* None */
+      jbyteArray v = bytes_of(env, rl + off[i], (jsize)(off[i + 1] - off[i]));
+      if (!v) break; /* OutOfMemoryError pending */
+      (*env)->SetObjectArrayElement(env, out, i, v);
+      (*env)->DeleteLocalRef(env, v);
+    }
+  }
+  free(rl);
+  bufs_free(&b);
+  if (rc != KH_OK) throw_kh(env, rc);
+  return out;
+}
+
 /* ---- versions (Ledger.scala:237-271 retry / reject; TrieAccounts.rootHash; copy) ---- */
 JNIEXPORT jint JNICALL Java_khipu_trie_gpu_Khst_savepoint(JNIEnv* env, jclass cls, jlong handle) {
   (void)cls;

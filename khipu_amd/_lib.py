@@ -21,6 +21,7 @@ KH_HASH_KEYS = 0x1
 KH_EMIT_NODES = 0x2
 KH_SHARD_RCCL = 0x4  # kh_trie_root_sharded: the RCCL exchange even when a device repeats (tests' loopback)
 KH_NO_TRIE = 0xFFFFFFFF
+KH_EXPORT_VERIFY = 0x1  # kh_trie_export_nodes: re-hash every encoding against its cached reference
 
 # every symbol include/khst.h declares
 EXPORTS = (
@@ -34,7 +35,7 @@ EXPORTS = (
     "kh_trie_root_sharded", "kh_block_commit_host", "kh_dev_list_roots", "kh_trie_get", "kh_trie_get_host",
     "kh_dev_synth_storage", "kh_trie_roots_segmented_sharded", "kh_trie_savepoint", "kh_trie_rollback",
     "kh_trie_release", "kh_trie_savepoint_depth", "kh_trie_root_of", "kh_trie_root_of_host", "kh_trie_copy",
-    "kh_verify_nodes_packed", "kh_trie_usage", "kh_trie_compact",
+    "kh_verify_nodes_packed", "kh_trie_usage", "kh_trie_compact", "kh_trie_export_nodes", "kh_trie_nodes_by_hash",
 )
 
 
@@ -63,6 +64,11 @@ class KhTrieUsage(ctypes.Structure):
     """kh_trie_usage_t: a resident handle's records, value heap and HBM (include/khst.h)."""
     _fields_ = [(f, ctypes.c_uint64) for f in
                 ("records", "live_records", "heap_bytes", "live_heap_bytes", "map_slots", "hbm_bytes")]
+
+
+class KhExportCursor(ctypes.Structure):
+    """kh_export_cursor: zeroed to start; bound to the handle's version by the first call."""
+    _fields_ = [("next", ctypes.c_uint64), ("epoch", ctypes.c_uint64)]
 
 
 class KhStats(ctypes.Structure):
@@ -153,6 +159,9 @@ def lib():
     L.kh_trie_usage.argtypes = [vp, ctypes.POINTER(KhTrieUsage)]
     L.kh_trie_compact.argtypes = [vp, ctypes.POINTER(KhTrieUsage)]
     L.kh_verify_nodes_packed.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.kh_trie_export_nodes.argtypes = [vp, u32, u32, ctypes.POINTER(KhExportCursor), vp, u64, vp, u64, vp,
+                                       ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32)]
+    L.kh_trie_nodes_by_hash.argtypes = [vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

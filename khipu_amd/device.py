@@ -186,6 +186,69 @@ class _Versioned:
         check(lib().kh_trie_compact(self.h, ctypes.byref(u)))
         return {"records": int(u.records), "heap_bytes": int(u.heap_bytes)}
 
+    def export_cursor(self):
+        """A fresh kh_export_cursor for export_chunk."""
+        return _lib.KhExportCursor()
+
+    def export_chunk(self, cur, trie=None, verify=False, node_cap=1 << 16, rlp_cap=1 << 23):
+        """One kh_trie_export_nodes call: ([(hash, encoding)], done).  KH_ENOSPC (not even the next
+        record's nodes fit) and KH_EINVAL (a cursor from before a commit, rollback or compaction)
+        raise; the cursor is then unchanged."""
+        hs = np.zeros(32 * max(node_cap, 1), np.uint8)
+        rl = np.zeros(max(rlp_cap, 1), np.uint8)
+        of = np.zeros(node_cap + 1, np.uint64)
+        nn, nl, done = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        self.ctx._sync()
+        rc = lib().kh_trie_export_nodes(self.h, _lib.KH_NO_TRIE if trie is None else int(trie),
+                                        _lib.KH_EXPORT_VERIFY if verify else 0, ctypes.byref(cur), hs.ctypes.data,
+                                        node_cap, rl.ctypes.data, rlp_cap, of.ctypes.data, ctypes.byref(nn),
+                                        ctypes.byref(nl), ctypes.byref(done))
+        if rc == _lib.KH_ENOSPC:
+            e = _lib.KhError(rc, lib().kh_last_error().decode(errors="replace"))
+            e.needed = (int(nn.value), int(nl.value))
+            raise e
+        check(rc)
+        return [(hs[32 * i:32 * i + 32].tobytes(), rl[of[i]:of[i + 1]].tobytes()) for i in range(nn.value)], bool(done.value)
+
+    def export_nodes(self, trie=None, verify=False, node_cap=1 << 16, rlp_cap=1 << 23):
+        """Every node of the current version a node store needs, as (hash, encoding) pairs
+        (kh_trie_export_nodes driven to the end; the buffers grow when one record's nodes do not
+        fit).  trie: one trie id of a forest (None: all).  verify: every encoding is re-hashed on
+        the device against the reference its record caches."""
+        cur = self.export_cursor()
+        done = False
+        while not done:
+            try:
+                pairs, done = self.export_chunk(cur, trie, verify, node_cap, rlp_cap)
+            except _lib.KhError as e:
+                if e.code != _lib.KH_ENOSPC:
+                    raise
+                node_cap, rlp_cap = max(node_cap, e.needed[0]), max(rlp_cap, e.needed[1])
+                continue
+            yield from pairs
+
+    def nodes_by_hash(self, hashes):
+        """getMptNodeByHash over the current version (kh_trie_nodes_by_hash): [encoding or None]
+        per 32-byte hash, at most 4096 a call."""
+        hashes = list(hashes)
+        n = len(hashes)
+        hb = np.frombuffer(b"".join(hashes) + b"\0", np.uint8).copy()
+        found = np.zeros(max(n, 1), np.uint8)
+        off = np.zeros(n + 1, np.uint64)
+        need = ctypes.c_uint64(0)
+        cap = 0
+        self.ctx._sync()
+        for _ in range(2):
+            rl = np.zeros(max(cap, 1), np.uint8)
+            rc = lib().kh_trie_nodes_by_hash(self.h, hb.ctypes.data, n, found.ctypes.data, rl.ctypes.data, cap,
+                                             off.ctypes.data, ctypes.byref(need))
+            if rc == _lib.KH_ENOSPC:
+                cap = need.value
+                continue
+            check(rc)
+            return [rl[off[i]:off[i + 1]].tobytes() if found[i] else None for i in range(n)]
+        raise RuntimeError("kh_trie_nodes_by_hash: size negotiation failed")
+
 
 class ResidentTrie(_Versioned):
     """A trie kept in HBM between commits (kh_trie_open / kh_trie_apply).
@@ -278,6 +341,11 @@ class ResidentTrie(_Versioned):
         """{hash: encoding} written back by the last commit (kh_trie_emit_nodes): the nodes it
         created, every one reachable from the new root with an encoding >= 32 B, plus a changed root."""
         return emitted_nodes(lambda *a: lib().kh_trie_emit_nodes(self.h, *a))
+
+    def checkpoint(self, verify=False):
+        """(root, {hash: encoding}): the whole resumable state of the current version (a state
+        root plus its node store), what from_nodes opens again.  An empty trie: (EMPTY_TRIE_HASH, {})."""
+        return self.get_root(), dict(self.export_nodes(verify=verify))
 
     def root_of(self, upserts=(), deletes=(), stats=None):
         """TrieAccounts.rootHash (TrieAccounts.scala:73-80): the root commit(upserts, deletes)
