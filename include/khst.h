@@ -26,6 +26,9 @@
  *                           (khipu-eth/.../domain/Blockchain.scala:356-357, HostService.scala:103-112)
  *   kh_trie_export_nodes    the node store of a resident trie's current version (checkpoint; the
  *                           resume half is kh_trie_open_nodes)
+ *   kh_trie_prove           the nodes MerklePatriciaTrie.get visits (MerklePatriciaTrie.scala:90-147)
+ *                           for a batch of keys: an eth_getProof answer, or a block's witness
+ *   kh_verify_proofs        that walk re-done from a root over the listed nodes alone
  *
  * Semantics shared by every trie entry point:
  *   - input i is a put(key_i, value_i); later inputs overwrite earlier ones with the
@@ -428,6 +431,55 @@ int kh_trie_export_nodes(kh_trie* h, uint32_t trie_filter, uint32_t flags, kh_ex
  * KH_ENOSPC writes only *rlp_len. */
 int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8_t* found,
                           uint8_t* rlp, uint64_t rlp_cap, uint64_t* off, uint64_t* rlp_len);
+
+/* ---- Merkle proofs: the nodes on a key's path, and their check against a root ----
+ * The proof of a key is the list of nodes MerklePatriciaTrie.get visits from the trie's root,
+ * root first, restricted to the nodes a node store holds (encoding >= 32 B, plus the root node;
+ * a node embedded in its parent is part of the parent's bytes).  The walk ends at the leaf it
+ * reaches (whether or not its key matches), at an extension whose path the key leaves (listed),
+ * at a branch whose slot for the key's next nibble is empty, or at a value-only branch.  An empty
+ * trie, or a trie id a forest does not hold, gives an empty proof and found = 0.
+ *
+ * kh_trie_prove: n < 2^31 keys and trie ids exactly as in kh_trie_get_host; read-only on the
+ * handle (with a savepoint open it sees the commits since).  found[i] as in kh_trie_get.  The node
+ * table has the layout of kh_trie_root_nodes (node j: hash hashes32[32j..), encoding
+ * rlp[off[j]..off[j+1]), off of node_cap + 1 entries); the proof of key i is the table nodes
+ * path_idx[k], k in [path_off[i], path_off[i+1]) (path_off of n + 1 entries).  Without
+ * KH_PROVE_SHARED the table is the concatenation of the proofs (path_idx[k] == k).  With it every
+ * (record, node) appears once however many keys pass through it (a block witness), in ascending
+ * record order, the node a parent refers to before the branch under its extension; a node two
+ * tries of a forest hold comes once per trie.  At most 2^32 - 1 listed nodes a call (KH_EINVAL).
+ * When any capacity is short: KH_ENOSPC, and only *n_nodes, *rlp_len and *n_path are written (a
+ * retry with exactly those sizes succeeds). */
+#define KH_PROVE_SHARED 0x1u
+int kh_trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
+                  uint32_t flags, uint8_t* found,
+                  uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off,
+                  uint32_t* path_idx, uint64_t path_cap, uint64_t* path_off,
+                  uint64_t* n_nodes, uint64_t* rlp_len, uint64_t* n_path);
+
+/* kh_verify_proofs: needs no handle (a checker has no trie).  Key i (klen bytes; kec256'd with
+ * KH_HASH_KEYS in flags, else klen must be 32) is walked from roots32 (nroots = 1: one root for
+ * every key, or n: one per key) over its listed nodes, table and path arrays as kh_trie_prove
+ * returns them (plain or shared).  The first condition met, in walk order, decides status[i]:
+ * the next listed node must hash to the expected reference (the root at first); a 17-item list
+ * takes the key's next nibble (item 16 once the 64 nibbles are used up); a 2-item list is
+ * HexPrefix-decoded (flag nibble <= 3, a zero pad nibble, no path past nibble 64); an empty child
+ * item ends the walk (absent), a 32-byte string is the next expected reference, a list shorter
+ * than 32 B is walked in place, anything else is a bad node.  An empty proof is ABSENT iff the
+ * root is EMPTY_TRIE_HASH, else SHORT.  Values of the PROOF_VALUE keys are packed as in
+ * kh_trie_get_host (KH_ENOSPC writes only *val_bytes).  off or path_off not non-decreasing, or a
+ * node longer than 2^32 - 1 bytes: KH_EINVAL. */
+#define KH_PROOF_ABSENT 0   /* valid: the key is not in the trie */
+#define KH_PROOF_VALUE 1    /* valid: the value is returned */
+#define KH_PROOF_BAD_HASH 2 /* a listed node's kec256 is not the reference that leads to it (the root for the first) */
+#define KH_PROOF_BAD_NODE 3 /* a node on the walk is not a well-formed trie node, or a path index >= n_nodes */
+#define KH_PROOF_SHORT 4    /* the walk reaches a hash reference and the list has no further node */
+#define KH_PROOF_EXTRA 5    /* the walk ends before the list does */
+int kh_verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t* keys, uint32_t klen, uint64_t n,
+                     uint32_t flags, const uint8_t* rlp, const uint64_t* off, uint64_t n_nodes,
+                     const uint32_t* path_idx, const uint64_t* path_off,
+                     uint8_t* status, uint8_t* vals, uint64_t val_cap, uint64_t* voff, uint64_t* val_bytes);
 
 /* HBM held by a resident trie or forest.  Records and the value heap are append-only between
  * compactions: a commit appends the records and values it makes and leaves the ones it

@@ -945,6 +945,118 @@ JNIEXPORT jobjectArray JNICALL Java_khipu_trie_gpu_Khst_nodesByHash(JNIEnv* env,
   return out;
 }
 
+/* Merkle proofs of keys.length / klen keys (trie: a forest's trie ids, or null) into the caller's
+ * arrays: found[n], the node table (hashes / rlp / off as exportNodes fills them), pathIdx and
+ * pathOff[n + 1] -- the proof of key i is the table nodes pathIdx[k], k in [pathOff[i],
+ * pathOff[i + 1]), root first.  flags: KH_PROVE_SHARED (a block witness: every node once).
+ * sizes[0..2] = nodes / RLP bytes / path entries.  Returns the node count, or -1 when an array is
+ * too small (sizes hold what the call needs: grow and call again). */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_prove(JNIEnv* env, jclass cls, jlong handle, jintArray trie,
+                                                      jbyteArray keys, jint klen, jint flags, jbyteArray found,
+                                                      jbyteArray hashes, jbyteArray rlp, jlongArray off,
+                                                      jintArray pathIdx, jlongArray pathOff, jlongArray sizes) {
+  (void)cls;
+  if (klen <= 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "prove: klen must be positive");
+    return 0;
+  }
+  const uint64_t n = (uint64_t)len_of(env, keys) / (uint64_t)klen;
+  if ((uint64_t)len_of(env, found) < n || (uint64_t)len_of(env, pathOff) < n + 1 ||
+      (trie && (uint64_t)len_of(env, trie) < n) || len_of(env, off) < 1) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "prove: found / pathOff / trie / off shorter than the keys need");
+    return 0;
+  }
+  uint64_t node_cap = (uint64_t)len_of(env, hashes) / 32;
+  if ((uint64_t)len_of(env, off) - 1 < node_cap) node_cap = (uint64_t)len_of(env, off) - 1;
+  const uint64_t rlp_cap = (uint64_t)len_of(env, rlp), path_cap = (uint64_t)len_of(env, pathIdx);
+  Bufs b = {0};
+  const uint32_t* tr = in_i(env, &b, trie);
+  const uint8_t* ks = in_b(env, &b, keys);
+  uint8_t* fd = out_buf(env, &b, found, 1);
+  uint8_t* hs = out_buf(env, &b, hashes, 1);
+  uint8_t* rl = out_buf(env, &b, rlp, 1);
+  uint64_t* of = out_buf(env, &b, off, 8);
+  uint32_t* pi = out_buf(env, &b, pathIdx, 4);
+  uint64_t* po = out_buf(env, &b, pathOff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t nn = 0, nb = 0, np = 0;
+  const int rc = kh_trie_prove(H(handle), tr, ks, (uint32_t)klen, n, (uint32_t)flags, fd, hs, node_cap, rl, rlp_cap, of,
+                               pi, path_cap, po, &nn, &nb, &np);
+  if (rc == KH_OK) {
+    put_b(env, found, fd, n);
+    put_b(env, hashes, hs, 32 * nn);
+    put_b(env, rlp, rl, nb);
+    put_l(env, off, of, nn + 1);
+    put_i(env, pathIdx, pi, np);
+    put_l(env, pathOff, po, n + 1);
+  }
+  bufs_free(&b);
+  const jlong sz[3] = {(jlong)nn, (jlong)nb, (jlong)np};
+  put_l(env, sizes, sz, 3);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)nn;
+}
+
+/* The proofs prove returned (or a peer sent) checked against roots (32 bytes: one root for every
+ * key; or 32 per key): status[i] one of KH_PROOF_*, the values of the KH_PROOF_VALUE keys packed
+ * into vals with voff[n + 1].  nNodes table nodes in rlp / off.  flags: KH_HASH_KEYS.  Returns the
+ * value bytes written, or -1 when vals is too small (sizes[0] holds the bytes needed). */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_verifyProofs(JNIEnv* env, jclass cls, jbyteArray roots,
+                                                             jbyteArray keys, jint klen, jint flags, jbyteArray rlp,
+                                                             jlongArray off, jint nNodes, jintArray pathIdx,
+                                                             jlongArray pathOff, jbyteArray status, jbyteArray vals,
+                                                             jlongArray voff, jlongArray sizes) {
+  (void)cls;
+  if (klen <= 0 || nNodes < 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyProofs: klen must be positive, nNodes not negative");
+    return 0;
+  }
+  const uint64_t n = (uint64_t)len_of(env, keys) / (uint64_t)klen, nroots = (uint64_t)len_of(env, roots) / 32;
+  if ((uint64_t)len_of(env, status) < n || (uint64_t)len_of(env, voff) < n + 1 ||
+      (uint64_t)len_of(env, pathOff) < n + 1 || (uint64_t)len_of(env, off) < (uint64_t)nNodes + 1) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyProofs: status / voff / pathOff / off too short");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint8_t* rt = in_b(env, &b, roots);
+  const uint8_t* ks = in_b(env, &b, keys);
+  const uint8_t* rl = in_b(env, &b, rlp);
+  const uint64_t* of = in_l(env, &b, off);
+  const uint32_t* pi = in_i(env, &b, pathIdx);
+  const uint64_t* po = in_l(env, &b, pathOff);
+  uint8_t* st = out_buf(env, &b, status, 1);
+  uint8_t* vl = out_buf(env, &b, vals, 1);
+  uint64_t* vo = out_buf(env, &b, voff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  /* the library reads rlp up to off[nNodes] and pathIdx up to pathOff[n] */
+  if (of[nNodes] > (uint64_t)len_of(env, rlp) || po[n] > (uint64_t)len_of(env, pathIdx)) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyProofs: off / pathOff point past rlp / pathIdx");
+    return 0;
+  }
+  uint64_t need = 0;
+  const int rc = kh_verify_proofs(rt, nroots, ks, (uint32_t)klen, n, (uint32_t)flags, rl, of, (uint64_t)nNodes, pi, po,
+                                  st, vl, (uint64_t)len_of(env, vals), vo, &need);
+  if (rc == KH_OK) {
+    put_b(env, status, st, n);
+    put_b(env, vals, vl, need);
+    put_l(env, voff, vo, n + 1);
+  }
+  bufs_free(&b);
+  const jlong sz[1] = {(jlong)need};
+  put_l(env, sizes, sz, 1);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)need;
+}
+
 /* ---- versions (Ledger.scala:237-271 retry / reject; TrieAccounts.rootHash; copy) ---- */
 JNIEXPORT jint JNICALL Java_khipu_trie_gpu_Khst_savepoint(JNIEnv* env, jclass cls, jlong handle) {
   (void)cls;

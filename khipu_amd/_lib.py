@@ -22,6 +22,14 @@ KH_EMIT_NODES = 0x2
 KH_SHARD_RCCL = 0x4  # kh_trie_root_sharded: the RCCL exchange even when a device repeats (tests' loopback)
 KH_NO_TRIE = 0xFFFFFFFF
 KH_EXPORT_VERIFY = 0x1  # kh_trie_export_nodes: re-hash every encoding against its cached reference
+KH_PROVE_SHARED = 0x1  # kh_trie_prove: every (record, node) once in the table (a block witness)
+# kh_verify_proofs statuses
+KH_PROOF_ABSENT = 0     # valid: the key is not in the trie
+KH_PROOF_VALUE = 1      # valid: the value is returned
+KH_PROOF_BAD_HASH = 2   # a listed node does not hash to the reference that leads to it
+KH_PROOF_BAD_NODE = 3   # a node on the walk is not a well-formed trie node, or a path index >= n_nodes
+KH_PROOF_SHORT = 4      # the walk reaches a hash reference and the list has no further node
+KH_PROOF_EXTRA = 5      # the walk ends before the list does
 
 # every symbol include/khst.h declares
 EXPORTS = (
@@ -36,6 +44,7 @@ EXPORTS = (
     "kh_dev_synth_storage", "kh_trie_roots_segmented_sharded", "kh_trie_savepoint", "kh_trie_rollback",
     "kh_trie_release", "kh_trie_savepoint_depth", "kh_trie_root_of", "kh_trie_root_of_host", "kh_trie_copy",
     "kh_verify_nodes_packed", "kh_trie_usage", "kh_trie_compact", "kh_trie_export_nodes", "kh_trie_nodes_by_hash",
+    "kh_trie_prove", "kh_verify_proofs",
 )
 
 
@@ -162,6 +171,10 @@ def lib():
     L.kh_trie_export_nodes.argtypes = [vp, u32, u32, ctypes.POINTER(KhExportCursor), vp, u64, vp, u64, vp,
                                        ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32)]
     L.kh_trie_nodes_by_hash.argtypes = [vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64)]
+    L.kh_trie_prove.argtypes = [vp, vp, vp, u32, u64, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp,
+                                ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.kh_verify_proofs.argtypes = [vp, u64, vp, u32, u64, u32, vp, vp, u64, vp, vp, vp, vp, u64, vp,
+                                   ctypes.POINTER(u64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

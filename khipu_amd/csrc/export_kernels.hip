@@ -90,11 +90,13 @@ __global__ void __launch_bounds__(BS) k_export_fit(const uint32_t* cpos, const u
 
 // Write: the encodings of items [0, n) at their scanned places, cooperatively over the 16 lanes.
 // Export (hashes / off non-NULL): node slot cpos[i] (+1); by hash (found non-NULL): the encoding
-// of query i at bpos[i].
+// of query i at bpos[i].  A list with hashes / off (a proof's hits): item i is node slot i, at
+// bpos64[i] when the 64-bit scan is given (the bytes of a call's proofs may pass 2^32).
 __global__ void __launch_bounds__(BS) k_export_write(Recs R, const uint8_t* heap, const uint64_t* list, uint64_t r0,
                                                      uint64_t n, uint32_t filter, const uint32_t* stash,
                                                      const uint32_t* cpos, const uint32_t* bpos, uint8_t* hashes,
-                                                     uint8_t* rlp, uint64_t* off, uint8_t* found) {
+                                                     uint8_t* rlp, uint64_t* off, uint8_t* found,
+                                                     const uint64_t* bpos64) {
   const uint64_t i = (uint64_t)blockIdx.x * GROUPS + threadIdx.x / EXP_LANES;
   const uint32_t lane = threadIdx.x % EXP_LANES;
   const bool in = i < n;
@@ -109,9 +111,17 @@ __global__ void __launch_bounds__(BS) k_export_write(Recs R, const uint8_t* heap
   if (in && found && lane == 0) found[i] = sel != 0;
   if (!sel) return;
   uint32_t len[2];
-  const uint64_t at = bpos[i];
+  const uint64_t at = bpos64 ? bpos64[i] : bpos[i];
   exp_write(R, heap, r, sel, lane, child, pre, S, rlp + at, len);
   if (!hashes || lane >= 2) return;
+  if (list) {  // one node an item
+    if (lane) return;
+    const ulonglong2* h = (const ulonglong2*)exp_hash_of(R, r, sel);
+    ((ulonglong2*)(hashes + 32 * i))[0] = h[0];
+    ((ulonglong2*)(hashes + 32 * i))[1] = h[1];
+    off[i] = at;
+    return;
+  }
   // lane 0 / lane 1: the hash and offset of the first / second node written
   const uint32_t first = (sel & EXP_UPPER) ? EXP_UPPER : EXP_LOWER;
   if (lane == 1 && sel != (EXP_UPPER | EXP_LOWER)) return;

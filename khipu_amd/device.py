@@ -388,6 +388,12 @@ class ResidentTrie(_Versioned):
         """Batched get (kh_trie_get): [value or None] per key (raw keys with hash_keys)."""
         return trie_get(self.h, keys)
 
+    def prove(self, keys, shared=False):
+        """Merkle proofs (kh_trie_prove): (found, proofs), proofs[i] the node encodings on key i's
+        path, root first; with shared=True also the ProofTable whose nodes each appear once."""
+        self.ctx._sync()
+        return _prove(self.h, keys, None, shared)
+
     @property
     def root_hash(self):
         return self.root
@@ -431,6 +437,112 @@ def trie_get(h, keys, trie_ids=None):
         check(rc)
         return [vals[voff[i]:voff[i + 1]].tobytes() if found[i] else None for i in range(n)]
     raise RuntimeError("kh_trie_get: size negotiation failed")
+
+
+class ProofTable:
+    """The node table of a kh_trie_prove call and the paths into it: nodes[j] has hash hashes[j];
+    the proof of key i is nodes[path_idx[k]] for k in [path_off[i], path_off[i + 1])."""
+
+    def __init__(self, hashes, nodes, path_idx, path_off):
+        self.hashes, self.nodes = hashes, nodes
+        self.path_idx = np.asarray(path_idx, np.uint32)
+        self.path_off = np.asarray(path_off, np.uint64)
+
+    def proof(self, i):
+        return [self.nodes[j] for j in self.path_idx[int(self.path_off[i]):int(self.path_off[i + 1])]]
+
+    def proofs(self):
+        return [self.proof(i) for i in range(len(self.path_off) - 1)]
+
+
+def trie_prove_raw(h, keys, trie_ids=None, shared=False, caps=None):
+    """One kh_trie_prove call with the capacities caps = (nodes, encoding bytes, path entries):
+    (rc, (n_nodes, rlp_len, n_path), arrays), arrays = (found, hashes, rlp, off, path_idx, path_off)."""
+    keys = list(keys)
+    n = len(keys)
+    klen = len(keys[0]) if keys else 32
+    kb = np.frombuffer(b"".join(keys) + b"\0", np.uint8).copy()
+    tb = np.asarray(trie_ids, np.uint32) if trie_ids is not None else None
+    cn, cb, cp = caps or (0, 0, 0)
+    found = np.zeros(max(n, 1), np.uint8)
+    hs = np.zeros(32 * max(cn, 1), np.uint8)
+    rl = np.zeros(max(cb, 1), np.uint8)
+    of = np.zeros(cn + 1, np.uint64)
+    pi = np.zeros(max(cp, 1), np.uint32)
+    po = np.zeros(n + 1, np.uint64)
+    nn, nl, npth = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().kh_trie_prove(h, tb.ctypes.data if tb is not None else None, kb.ctypes.data, klen, n,
+                             _lib.KH_PROVE_SHARED if shared else 0, found.ctypes.data, hs.ctypes.data, cn,
+                             rl.ctypes.data, cb, of.ctypes.data, pi.ctypes.data, cp, po.ctypes.data,
+                             ctypes.byref(nn), ctypes.byref(nl), ctypes.byref(npth))
+    return rc, (int(nn.value), int(nl.value), int(npth.value)), (found, hs, rl, of, pi, po)
+
+
+def trie_prove(h, keys, trie_ids=None, shared=False):
+    """Merkle proofs through kh_trie_prove (sizes negotiated): (found, ProofTable)."""
+    keys = list(keys)
+    caps = None
+    for _ in range(3):
+        rc, sizes, (found, hs, rl, of, pi, po) = trie_prove_raw(h, keys, trie_ids, shared, caps)
+        if rc == _lib.KH_ENOSPC:
+            caps = sizes
+            continue
+        check(rc)
+        nn, _, npth = sizes
+        table = ProofTable([hs[32 * j:32 * j + 32].tobytes() for j in range(nn)],
+                           [rl[int(of[j]):int(of[j + 1])].tobytes() for j in range(nn)], pi[:npth].copy(), po)
+        return [bool(f) for f in found[:len(keys)]], table
+    raise RuntimeError("kh_trie_prove: size negotiation failed")
+
+
+def _prove(h, keys, trie_ids, shared):
+    found, table = trie_prove(h, keys, trie_ids, shared)
+    return (found, table.proofs(), table) if shared else (found, table.proofs())
+
+
+def verify_proofs(roots, keys, proofs_or_table, hash_keys=False):
+    """kh_verify_proofs: (status, values) per key, values[i] the bytes where status[i] is
+    KH_PROOF_VALUE, else None.  roots: one 32-byte root for every key, or a list of one per key;
+    proofs_or_table: a list of proofs (each a list of node encodings, root first) or the
+    ProofTable a shared prove returned."""
+    keys = list(keys)
+    n = len(keys)
+    if isinstance(roots, (bytes, bytearray)):
+        roots = [bytes(roots)]
+    roots = list(roots)
+    if isinstance(proofs_or_table, ProofTable):
+        nodes, pi, po = proofs_or_table.nodes, proofs_or_table.path_idx, proofs_or_table.path_off
+    else:
+        nodes = [e for p in proofs_or_table for e in p]
+        pi = np.arange(len(nodes), dtype=np.uint32)
+        po = np.zeros(n + 1, np.uint64)
+        np.cumsum([len(p) for p in proofs_or_table], out=po[1:])
+    klen = len(keys[0]) if keys else 32
+    kb = np.frombuffer(b"".join(keys) + b"\0", np.uint8).copy()
+    rb = np.frombuffer(b"".join(roots) + b"\0", np.uint8).copy()
+    rl = np.frombuffer(b"".join(nodes) + b"\0", np.uint8).copy()
+    of = np.zeros(len(nodes) + 1, np.uint64)
+    np.cumsum([len(e) for e in nodes], out=of[1:])
+    pi = np.ascontiguousarray(np.append(pi, np.uint32(0)), np.uint32)
+    po = np.ascontiguousarray(po, np.uint64)
+    status = np.zeros(max(n, 1), np.uint8)
+    voff = np.zeros(n + 1, np.uint64)
+    need = ctypes.c_uint64(0)
+    cap = 0
+    for _ in range(2):
+        vals = np.zeros(max(cap, 1), np.uint8)
+        rc = lib().kh_verify_proofs(rb.ctypes.data, len(roots), kb.ctypes.data, klen, n,
+                                    _lib.KH_HASH_KEYS if hash_keys else 0, rl.ctypes.data, of.ctypes.data, len(nodes),
+                                    pi.ctypes.data, po.ctypes.data, status.ctypes.data, vals.ctypes.data, cap,
+                                    voff.ctypes.data, ctypes.byref(need))
+        if rc == _lib.KH_ENOSPC:
+            cap = need.value
+            continue
+        check(rc)
+        st = [int(s) for s in status[:n]]
+        return st, [vals[int(voff[i]):int(voff[i + 1])].tobytes() if st[i] == _lib.KH_PROOF_VALUE else None
+                    for i in range(n)]
+    raise RuntimeError("kh_verify_proofs: size negotiation failed")
 
 
 def emitted_nodes(call):
@@ -493,6 +605,13 @@ class ResidentForest(_Versioned):
         """queries: [(trie_id, key)] -> [value or None] (kh_trie_get)."""
         q = list(queries)
         return trie_get(self.h, [k for _, k in q], [t for t, _ in q])
+
+    def prove(self, queries, shared=False):
+        """queries: [(trie_id, key)] -> (found, proofs[, ProofTable]) as ResidentTrie.prove, each
+        proof under its own trie's root."""
+        q = list(queries)
+        self.ctx._sync()
+        return _prove(self.h, [k for _, k in q], [t for t, _ in q], shared)
 
     def last_roots(self):
         """{trie_id: root} of the last commit (kh_forest_last_roots; also after block_commit)."""
