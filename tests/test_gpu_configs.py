@@ -12,7 +12,9 @@ def storage_tries(rng, ntries, lo=1, hi=10_000):
     key = kec256(32-byte big-endian slot index) (hashDataWordSerializable,
     trie/package.scala:34-36) -> raw 32-byte keys hashed on the device; value =
     RLP(trimmed 1-32 random bytes) (rlpDataWordSerializer, trie/package.scala:28-32), so
-    1-byte values < 0x80 (inline leaves) occur."""
+    1-byte values < 0x80 occur.  They do not make inline leaves here: a leaf is shorter than
+    32 bytes only under a branch at depth >= 8, and hashed keys in tries of at most 10,000
+    slots practically never share 8 nibbles (tests/test_gpu_levels.py builds such leaves)."""
     cnt = np.exp(rng.uniform(np.log(lo), np.log(hi + 1), ntries)).astype(np.int64).clip(lo, hi)
     seg_off = np.zeros(ntries + 1, np.uint64)
     seg_off[1:] = np.cumsum(cnt)
