@@ -26,6 +26,11 @@
  *                           (khipu-eth/.../domain/Blockchain.scala:356-357, HostService.scala:103-112)
  *   kh_trie_export_nodes    the node store of a resident trie's current version (checkpoint; the
  *                           resume half is kh_trie_open_nodes)
+ *   kh_forest_load_nodes    MerklePatriciaTrie(account.stateRoot, storageSource) for many contracts
+ *                           at once (MerklePatriciaTrie.scala:60-66,520-542): storage tries paged
+ *                           into a resident forest by (trie id, storage root), or a whole forest
+ *                           resumed from a checkpoint; kh_forest_roots lists what is resident,
+ *                           kh_forest_evict drops cold tries again
  *   kh_trie_prove           the nodes MerklePatriciaTrie.get visits (MerklePatriciaTrie.scala:90-147)
  *                           for a batch of keys: an eth_getProof answer, or a block's witness
  *   kh_verify_proofs        that walk re-done from a root over the listed nodes alone
@@ -326,6 +331,52 @@ int kh_forest_apply_host(kh_trie* f, const uint32_t* up_trie, const uint8_t* up_
 
 /* The touched tries and roots of a forest's last commit (also after kh_block_commit). */
 int kh_forest_last_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries);
+
+/* ---- forest load, roots and eviction: the working set of storage tries paged in and out ----
+ * MerklePatriciaTrie(account.stateRoot, storageSource) per contract (MerklePatriciaTrie.scala:
+ * 60-66,520-542), batched: k tries (id tries[j], root roots32[32j..), host arrays) are decoded
+ * from one node store (the layout of kh_trie_open_nodes: n encodings, content addressed; it may
+ * hold unrelated nodes and duplicates) into the forest, beside the tries it holds.  A node two
+ * listed tries share is decoded once per trie.  A root equal to EMPTY_TRIE_HASH loads nothing.
+ * All or nothing: on any error the forest is exactly as before.
+ *   KH_EINVAL, before anything is decoded: not a forest; an id listed twice; an id that is already
+ *     resident; k or n >= 2^31.  While decoding: a node that is not a canonical secure-trie node (a
+ *     branch value anywhere but a value-only branch at depth 64, an embedded node of 32 B or more, a
+ *     path past nibble 64, ...), or a load that would pass 2^32 - 2 records.
+ *   KH_ENODE: the walk is level-synchronous (the roots are round 0) and stops after the first
+ *     round in which a hash reference is absent from the store; every missing reference of that
+ *     round is reported, one entry per reference: miss_idx[e] = the list index j, miss32[32e..)
+ *     the hash.  *n_missing = their number; at most miss_cap entries are written (any miss_cap of
+ *     them).  The caller fetches them and retries.
+ * Records are appended in a fixed order (round by round; in a round in frontier order, children
+ * in nibble order, the roots in list order): the same load into two fresh forests gives the same
+ * kh_trie_export_nodes order.  A successful load ends every export cursor, adds the loaded keys to
+ * kh_trie_size, and leaves the last commit's roots and write-back set as they were (a load creates
+ * no node).  With a savepoint open the load is journaled: kh_trie_rollback makes the loaded tries
+ * non-resident again, kh_trie_release keeps them.
+ * Device form: d_enc / d_off on the handle's context, d_off non-decreasing (a precondition); the
+ * _host form checks that (KH_EINVAL) before it stages them.  stats (nullable): n_inputs = k,
+ * n_leaves = the forest's keys, n_levels = the rounds, n_node_hashes = the store's nodes (each is
+ * hashed), t_total_ms = t_sort_ms (the list checks, store hashing and sort) + t_branch_ms (the
+ * rounds) + t_topo_ms (the anchor map). */
+int kh_forest_load_nodes(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                         const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                         uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing,
+                         kh_stats* stats);
+int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                              const uint8_t* enc, const uint64_t* off, uint64_t n,
+                              uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing,
+                              kh_stats* stats);
+/* Every trie the forest holds (>= 1 key), ascending ids, with its root: one streaming pass over
+ * the records, read-only on the handle.  KH_ENOSPC with *n_tries when cap is short. */
+int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries);
+/* Drop whole tries from HBM: their records die and their anchors leave the map (kh_trie_compact
+ * reclaims the space).  An id that is not resident is skipped; *n_evicted = the tries dropped.
+ * The caller owns residency: afterwards the id reads as an EMPTY trie (kh_trie_get finds nothing, a
+ * commit to it starts from empty), exactly like an id the forest never saw -- reload it with
+ * kh_forest_load_nodes before it is used again.  The last commit's roots and write-back set are
+ * untouched; export cursors end.  KH_EINVAL while a savepoint is open, as for kh_trie_compact. */
+int kh_forest_evict(kh_trie* f, const uint32_t* tries, uint64_t k, uint64_t* n_evicted);
 
 /* One block (BlockWorldState.flush, BlockWorldState.scala:243-252 then TrieAccounts.flush):
  * the storage ops into the forest, each touched trie's new root written into the stateRoot

@@ -735,6 +735,120 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_forestLastRoots(JNIEnv* env, jc
   return (jlong)nt;
 }
 
+/* Page storage tries into a forest (MerklePatriciaTrie(account.stateRoot, storageSource) per
+ * contract, batched): tries[j] with root roots[32j..) decoded from the node store enc / off (as
+ * openNodes).  All or nothing.  Nodes missing from the store: missIdxOut / missOut (nullable)
+ * receive the list index and hash of every missing reference of the round that stopped the walk
+ * (as many as fit), nMissingOut[0] (long[1], nullable) their number, and
+ * MPTNodeMissingException is thrown with the first listed hash.  dEnc != 0: the store is in HBM
+ * (device addresses of the encodings and the n + 1 offsets, on the forest's context). */
+static void forest_load(JNIEnv* env, jlong handle, jintArray tries, jbyteArray roots, jbyteArray enc, jlongArray off,
+                        jlong dEnc, jlong dOff, jlong dN, jintArray missIdxOut, jbyteArray missOut,
+                        jlongArray nMissingOut) {
+  const uint64_t k = (uint64_t)len_of(env, tries);
+  const jsize icap = len_of(env, missIdxOut), hcap = len_of(env, missOut) / 32;
+  const uint64_t cap = (uint64_t)(icap < hcap ? icap : hcap);
+  uint64_t nm = 0;
+  Bufs b = {0};
+  const uint32_t* t = in_i(env, &b, tries);
+  const uint8_t* r = in_b(env, &b, roots);
+  const uint8_t* e = dEnc ? NULL : in_b(env, &b, enc);
+  const uint64_t* o = dEnc ? NULL : in_l(env, &b, off);
+  uint32_t* mi = bufs_alloc(&b, 4 * (size_t)(cap ? cap : 1));
+  uint8_t* mh = bufs_alloc(&b, 32 * (size_t)(cap ? cap : 1));
+  if (bufs_failed(env, &b)) return;
+  if ((uint64_t)len_of(env, roots) < 32 * k) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "roots: 32 bytes per listed trie");
+    return;
+  }
+  if (cap) memset(mh, 0, 32);
+  const int rc = dEnc ? kh_forest_load_nodes(H(handle), t, r, k, (const uint8_t*)(intptr_t)dEnc,
+                                             (const uint64_t*)(intptr_t)dOff, (uint64_t)dN, mi, mh, cap, &nm, NULL)
+                      : kh_forest_load_nodes_host(H(handle), t, r, k, e, o, count_of(env, off), mi, mh, cap, &nm, NULL);
+  if (rc == KH_ENODE) {
+    const uint64_t w = nm < cap ? nm : cap;
+    const jlong n64 = (jlong)nm;
+    put_i(env, missIdxOut, mi, w);
+    put_b(env, missOut, mh, 32 * w);
+    put_l(env, nMissingOut, &n64, 1);
+  }
+  if (rc != KH_OK) throw_kh_hash(env, rc, cap && nm ? mh : NULL);
+  bufs_free(&b);
+}
+JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadNodes(JNIEnv* env, jclass cls, jlong handle, jintArray tries,
+                                                               jbyteArray roots, jbyteArray enc, jlongArray off,
+                                                               jintArray missIdxOut, jbyteArray missOut,
+                                                               jlongArray nMissingOut) {
+  (void)cls;
+  forest_load(env, handle, tries, roots, enc, off, 0, 0, 0, missIdxOut, missOut, nMissingOut);
+}
+JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadNodesDevice(JNIEnv* env, jclass cls, jlong handle,
+                                                                     jintArray tries, jbyteArray roots, jlong dEnc,
+                                                                     jlong dOff, jlong n, jintArray missIdxOut,
+                                                                     jbyteArray missOut, jlongArray nMissingOut) {
+  (void)cls;
+  if (!dEnc || !dOff) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "dEnc / dOff: device addresses");
+    return;
+  }
+  forest_load(env, handle, tries, roots, NULL, NULL, dEnc, dOff, n, missIdxOut, missOut, nMissingOut);
+}
+
+/* every trie the forest holds, ascending ids: 36 bytes a trie, the id (4 bytes, little endian)
+ * then its root.  The count is negotiated: KH_ENOSPC reports it, another thread's commit or load
+ * can change it again, so the loop grows and retries (bounded), as get does. */
+JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_forestRoots(JNIEnv* env, jclass cls, jlong handle) {
+  (void)cls;
+  uint64_t nt = 0, cap = 0;
+  uint32_t* t = NULL;
+  uint8_t* r = NULL;
+  int rc = KH_ENOSPC;
+  for (int tries = 0; rc == KH_ENOSPC && tries < 16; ++tries) { /* the first call reports the count */
+    rc = kh_forest_roots(H(handle), t, r, cap, &nt);
+    if (rc == KH_ENOSPC) {
+      free(t);
+      free(r);
+      cap = nt + nt / 8;
+      t = malloc(4 * (size_t)(cap ? cap : 1));
+      r = malloc(32 * (size_t)(cap ? cap : 1));
+      if (!t || !r) rc = KH_ENOMEM;
+    }
+  }
+  jbyteArray out = NULL;
+  uint8_t* packed = rc == KH_OK ? malloc(36 * (size_t)(nt ? nt : 1)) : NULL;
+  if (rc == KH_OK && !packed) rc = KH_ENOMEM;
+  if (rc == KH_OK) {
+    for (uint64_t i = 0; i < nt; ++i) {
+      for (int q = 0; q < 4; ++q) packed[36 * i + q] = (uint8_t)(t[i] >> (8 * q));
+      memcpy(packed + 36 * i + 4, r + 32 * i, 32);
+    }
+    out = bytes_of(env, packed, (jsize)(36 * nt));
+  }
+  free(packed);
+  free(t);
+  free(r);
+  if (rc != KH_OK) throw_kh(env, rc);
+  return out;
+}
+
+/* drop whole tries from HBM (the caller owns residency: an evicted id reads as an empty trie
+ * until forestLoadNodes brings it back); returns the number dropped */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_forestEvict(JNIEnv* env, jclass cls, jlong handle, jintArray tries) {
+  (void)cls;
+  uint64_t dropped = 0;
+  Bufs b = {0};
+  const uint32_t* t = in_i(env, &b, tries);
+  if (bufs_failed(env, &b)) return 0;
+  const int rc = kh_forest_evict(H(handle), t, (uint64_t)len_of(env, tries), &dropped);
+  bufs_free(&b);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)dropped;
+}
+
 /* One block (BlockWorldState.scala:243-252 then TrieAccounts.flush): storage ops into the
  * forest, the new storage roots written into the named account bodies (accTrie[i], -1 =
  * KH_NO_TRIE: none), the account ops into the state trie.  All or nothing.  Returns the state

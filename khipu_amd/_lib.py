@@ -44,7 +44,8 @@ EXPORTS = (
     "kh_dev_synth_storage", "kh_trie_roots_segmented_sharded", "kh_trie_savepoint", "kh_trie_rollback",
     "kh_trie_release", "kh_trie_savepoint_depth", "kh_trie_root_of", "kh_trie_root_of_host", "kh_trie_copy",
     "kh_verify_nodes_packed", "kh_trie_usage", "kh_trie_compact", "kh_trie_export_nodes", "kh_trie_nodes_by_hash",
-    "kh_trie_prove", "kh_verify_proofs",
+    "kh_trie_prove", "kh_verify_proofs", "kh_forest_load_nodes", "kh_forest_load_nodes_host", "kh_forest_roots",
+    "kh_forest_evict",
 )
 
 
@@ -175,6 +176,10 @@ def lib():
                                 ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.kh_verify_proofs.argtypes = [vp, u64, vp, u32, u64, u32, vp, vp, u64, vp, vp, vp, vp, u64, vp,
                                    ctypes.POINTER(u64)]
+    L.kh_forest_load_nodes.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.kh_forest_load_nodes_host.argtypes = L.kh_forest_load_nodes.argtypes
+    L.kh_forest_roots.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.kh_forest_evict.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

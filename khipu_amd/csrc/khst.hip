@@ -39,6 +39,7 @@
 #include "layout.h"
 #include "export.h"
 #include "prove.h"
+#include "load.h"
 
 using namespace khst;
 
@@ -6988,7 +6989,398 @@ static int verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t*
   return KH_OK;
 }
 
+// ---- forest load, roots and eviction (load.h; the kernels are csrc/load_kernels.hip's)
+__global__ void k_load_root_flags(const uint64_t* roots, uint64_t k, uint32_t* flag);
+__global__ void k_load_roots(const uint64_t* roots, uint64_t k, const uint32_t* flag, const uint32_t* pos, LItems N);
+__global__ void k_load_resident(AMap M, Recs R, const uint32_t* tries, uint64_t k, unsigned long long* n_resident);
+__global__ void k_load_count(LItems I, uint64_t ni, NStore S, LCounts C, unsigned long long* tot);
+__global__ void k_load_fill(LItems I, uint64_t ni, NStore S, LCounts C, LItems N, const uint32_t* tries, uint8_t* recs,
+                            uint64_t rbase, uint64_t rcap, uint8_t* heap, uint64_t hbase, uint64_t heap_cap);
+__global__ void k_load_missing(LItems I, uint64_t ni, const uint32_t* miss, const uint32_t* mpos, uint64_t cap,
+                               uint32_t* out_idx, uint64_t* out_hash);
+__global__ void k_roots_flags(Recs R, uint64_t n, uint32_t* flag);
+__global__ void k_roots_write(Recs R, uint64_t n, const uint32_t* flag, const uint32_t* pos, uint64_t cap,
+                              uint32_t* tries, uint64_t* roots);
+__global__ void k_evict_flags(Recs R, uint64_t n, const uint32_t* tries, uint32_t nt, uint32_t* flag,
+                              unsigned long long* cnt);
+__global__ void k_evict_list(uint64_t n, const uint32_t* flag, const uint32_t* pos, uint64_t cap, uint32_t* list);
+
+static LItems litems_carve(DevBuf& b, uint64_t cap) {
+  Layout L;
+  LItems I{};
+  L.add(I.pre, cap * 4);
+  L.add_all(cap, I.a, I.d);
+  L.add(I.ref, cap * 4);
+  L.add(I.rl, cap);
+  L.add(I.pref, cap * 4);
+  L.add(I.prl, cap);
+  L.add(I.j, cap);
+  place(b, L);
+  I.cap = cap;
+  return I;
+}
+
+// k tries (ids tries[j], roots roots32[32j..), host arrays) decoded from n stored node encodings
+// (device buffers) into forest h, beside what it holds.  All or nothing: a refusal or failure
+// before the anchor map is touched leaves no record past the old count (the slots cleared) and
+// every host-side field as it was.  With a savepoint open the map inserts are journaled.
+static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
+                        const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
+                        uint64_t* n_missing, kh_stats* stats) {
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (k >= (1ULL << 31) || n >= (1ULL << 31)) throw KhError{KH_EINVAL, "trie list or node store too large"};
+  {
+    std::vector<uint32_t> ids(tries, tries + k);
+    std::sort(ids.begin(), ids.end());
+    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
+      throw KhError{KH_EINVAL, "kh_forest_load_nodes: a trie id is listed twice"};
+  }
+  trie_settle(h);
+  if (k == 0) {
+    ++h->epoch;
+    return;
+  }
+  HIPCHK(hipEventRecord(c->ev[6], st));
+  // the list on the device, the roots to walk (not the empty trie's) and the resident check
+  Layout Lr;
+  uint32_t *dtries, *rflag, *rpos, *dmidx;
+  uint64_t *droots, *dmhash;
+  unsigned long long* tot;
+  char* rscr;
+  const uint64_t mcap = std::min<uint64_t>(miss_cap, 1ULL << 24);
+  Lr.add(dtries, k);
+  Lr.add(droots, k * 4);
+  Lr.add_all(k, rflag, rpos);
+  Lr.add(rscr, scan_scratch_bytes(k + 1, 4));
+  Lr.add(tot, 8);
+  Lr.add(dmidx, mcap + 1);
+  Lr.add(dmhash, (mcap + 1) * 4);
+  place(h->gbuf, Lr);
+  HIPCHK(hipMemcpyAsync(dtries, tries, k * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(droots, roots32, k * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
+  if (h->rn && h->mcap) {
+    hipLaunchKernelGGL(k_load_resident, GRID(k, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint32_t*)dtries, k,
+                       tot + 6);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_load_root_flags, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, rflag);
+  LAUNCH_CHECK();
+  scan_exclusive<uint32_t>(rflag, rpos, k, (uint32_t*)tot, rscr, st);
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->h_pinned[6]) throw KhError{KH_EINVAL, "kh_forest_load_nodes: a listed trie is already resident"};
+  uint64_t ni = (uint32_t)c->h_pinned[0];
+  uint32_t max_id = 0;
+  for (uint64_t j = 0; j < k; ++j) max_id = std::max(max_id, tries[j]);
+  if (ni == 0) {  // every root is the empty trie's
+    ++h->epoch;
+    return;
+  }
+  // the store, keyed by kec256 of each encoding (content addressed)
+  Layout L;
+  uint64_t* hs;
+  SortIO S{};
+  L.add(hs, n * 4 + 4);
+  S.declare(L, n, n * 4 + 4, false, n + 1, n + 1, CTR_N);
+  place(h->ws, L);
+  S.K32 = hs;
+  S.n = n;
+  HIPCHK(hipMemsetAsync(S.ctr, 0, CTR_N * 8, st));
+  NStore NS{nullptr, nullptr, 0, d_enc, d_off};
+  if (n) {
+    hipLaunchKernelGGL(k_kec_batch, GRID(n, BS), dim3(BS), 0, st, d_enc, d_off, n, hs);
+    LAUNCH_CHECK();
+    sort_dedup(c, S);
+    NS.hash = S.skey;
+    NS.idx = S.sidx;
+    NS.m = S.m;
+  }
+  HIPCHK(hipEventRecord(c->ev[0], st));  // (stats: the store is hashed and sorted)
+  const uint64_t rn0 = h->rn;
+  uint64_t heap_cur = h->heap_n, keys = 0;
+  uint32_t rounds = 0;
+  bool map_stage = false;
+  try {
+    DevBuf fa, fb, cb;
+    LItems cur = litems_carve(fa, ni);
+    hipLaunchKernelGGL(k_load_roots, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, (const uint32_t*)rflag,
+                       (const uint32_t*)rpos, cur);
+    LAUNCH_CHECK();
+    for (; ni && rounds < 80; ++rounds) {
+      // count, scans, one sync
+      Layout Lc;
+      LCounts C{};
+      uint32_t* mpos;
+      char* scr;
+      Lc.add_all(ni, C.child, C.rec);
+      Lc.add(C.val, ni);
+      Lc.add_all(ni, C.miss, C.src, mpos);
+      Lc.add(scr, scan_scratch_bytes(ni + 1, 8));
+      place(cb, Lc);
+      HIPCHK(hipMemsetAsync(tot, 0, 64, st));
+      hipLaunchKernelGGL(k_load_count, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, tot);
+      LAUNCH_CHECK();
+      scan_exclusive<uint32_t>(C.child, C.child, ni, (uint32_t*)tot, scr, st);
+      scan_exclusive<uint32_t>(C.rec, C.rec, ni, (uint32_t*)(tot + 1), scr, st);
+      scan_exclusive<uint64_t>(C.val, C.val, ni, (uint64_t*)(tot + 2), scr, st);
+      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      const uint64_t nchild = (uint32_t)c->h_pinned[0], nrec = (uint32_t)c->h_pinned[1], nval = c->h_pinned[2];
+      const uint64_t code = c->h_pinned[3], nmiss = c->h_pinned[4];
+      keys += c->h_pinned[5];
+      if (code == OPEN_VALUE) throw KhError{KH_EINVAL, "a branch with a value: not a secure trie"};
+      if (code) throw KhError{KH_EINVAL, "the store holds a node that is not a canonical secure-trie node"};
+      if (nmiss) {  // every missing reference of this round (MPTNodeMissingException), then stop
+        const uint64_t w = std::min(nmiss, mcap);
+        if (w) {
+          scan_exclusive<uint32_t>(C.miss, mpos, ni, (uint32_t*)(tot + 7), scr, st);
+          hipLaunchKernelGGL(k_load_missing, GRID(ni, BS), dim3(BS), 0, st, cur, ni, (const uint32_t*)C.miss,
+                             (const uint32_t*)mpos, w, dmidx, dmhash);
+          LAUNCH_CHECK();
+          HIPCHK(hipMemcpyAsync(miss_idx, dmidx, w * 4, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(miss32, dmhash, w * 32, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        if (n_missing) *n_missing = nmiss;
+        throw KhError{KH_ENODE, "node missing from the store (MPTNodeMissingException)"};
+      }
+      if (h->rn + nrec >= (uint64_t)NONE) throw KhError{KH_EINVAL, "the load passes the forest's record limit"};
+      // fill: the records, the values and the next frontier at exactly the scanned sizes
+      recs_reserve(h, h->rn + nrec + 16);
+      const uint64_t hneed = heap_cur + nval + 64;
+      if (hneed > h->heap.cap) regrow(h->heap, heap_cur, hneed + hneed / 4, st);
+      LItems nxt = litems_carve(rounds & 1 ? fa : fb, std::max<uint64_t>(nchild, 1));
+      hipLaunchKernelGGL(k_load_fill, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, nxt, (const uint32_t*)dtries,
+                         (uint8_t*)h->recs.p, h->rn, h->rcap, (uint8_t*)h->heap.p, heap_cur, (uint64_t)h->heap.cap);
+      LAUNCH_CHECK();
+      h->rn += nrec;  // (a later regrow keeps the records of the earlier rounds)
+      heap_cur += nval;
+      cur = nxt;
+      ni = nchild;
+    }
+    if (ni) throw KhError{KH_EINVAL, "node store deeper than a 32-byte key allows"};
+    // the anchor map: only the new records enter it; rebuilt when it would pass half load
+    const uint64_t nnew = h->rn - rn0;
+    HIPCHK(hipEventRecord(c->ev[1], st));  // (stats: the rounds are done)
+    map_stage = true;
+    if (h->mcap == 0 || 2 * (h->mused + nnew + 1024) > h->mcap) {
+      map_rebuild(h, 1024);  // (syncs; with a savepoint open its map_epoch bump is the journal entry)
+    } else if (nnew) {
+      uint64_t* ilog = nullptr;
+      if (!h->sps.empty()) {  // journal: no saved records, the inserts' slot log
+        JSeg js = journal_reserve(h, 0, nnew);
+        js.dpos = js.ipos = h->jmap_n;
+        js.dn = 0;
+        js.in = nnew;
+        ilog = (uint64_t*)h->jmap.p + 3 * js.ipos;
+        h->jsegs.push_back(js);
+        h->jmap_n += nnew;
+      }
+      h->merr.ensure(64);
+      unsigned long long* err = (unsigned long long*)h->merr.p;
+      HIPCHK(hipMemsetAsync(err, 0, 16, st));
+      hipLaunchKernelGGL(k_map_insert, GRID(nnew, BS), dim3(BS), 0, st, map_of(h), recs_of(h), rn0, nnew,
+                         (const uint32_t*)nullptr, (uint64_t)0, err, err + 1, ilog);
+      LAUNCH_CHECK();
+      HIPCHK(hipMemcpyAsync(c->h_pinned, err, 16, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (c->h_pinned[0]) throw KhError{KH_EINTERNAL, "anchor map insert failed"};
+      h->mused += c->h_pinned[1];
+    }
+  } catch (...) {
+    if (map_stage) {
+      h->broken = true;  // the map may hold part of the load: only a rollback or a free from here
+    } else {
+      if (h->rn > rn0) {
+        (void)hipMemsetAsync((uint8_t*)h->recs.p + rn0 * REC_BYTES, 0, (h->rn - rn0) * REC_BYTES, st);
+        (void)hipStreamSynchronize(st);
+      }
+      h->rn = rn0;
+    }
+    throw;
+  }
+  h->heap_n = heap_cur;
+  h->nleaves += keys;
+  h->tid_bits = std::max(h->tid_bits, std::min(bits_for((uint64_t)max_id + 1) + 2, 32u));
+  ++h->epoch;
+  HIPCHK(hipEventRecord(c->ev[7], st));
+  HIPCHK(hipEventSynchronize(c->ev[7]));
+  if (stats) {
+    stats->n_inputs = k;
+    stats->n_leaves = h->nleaves;
+    stats->n_levels = rounds;
+    stats->n_node_hashes = n;
+    stats->t_total_ms = ev_ms(c->ev[6], c->ev[7]);
+    stats->t_sort_ms = ev_ms(c->ev[6], c->ev[0]);    // list checks, store hashing and sort
+    stats->t_branch_ms = ev_ms(c->ev[0], c->ev[1]);  // the rounds
+    stats->t_topo_ms = ev_ms(c->ev[1], c->ev[7]);    // the anchor map
+  }
+}
+
+// every trie the forest holds, ascending ids, with its root (read-only on the handle)
+static int forest_roots(kh_trie* h, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries) {
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  const uint64_t n = h->rn;
+  *n_tries = 0;
+  if (n == 0) return KH_OK;
+  Layout L;
+  uint32_t *flag, *pos, *tot;
+  char* scr;
+  L.add_all(n, flag, pos);
+  L.add(scr, scan_scratch_bytes(n + 1, 4));
+  L.add(tot, 4);
+  place(h->gbuf, L);
+  const Recs R = recs_of(h);
+  hipLaunchKernelGGL(k_roots_flags, GRID(n, BS), dim3(BS), 0, st, R, n, flag);
+  LAUNCH_CHECK();
+  scan_exclusive<uint32_t>(flag, pos, n, tot, scr, st);
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t nt = (uint32_t)c->h_pinned[0];
+  *n_tries = nt;
+  if (nt > cap || (nt && (!h_tries || !h_roots32))) return set_err(KH_ENOSPC, "trie output too small");
+  if (nt == 0) return KH_OK;
+  Layout Lo;
+  uint32_t* dt;
+  uint64_t* dr;
+  Lo.add(dt, nt);
+  Lo.add(dr, nt * 4);
+  place(h->xbuf, Lo);
+  hipLaunchKernelGGL(k_roots_write, GRID(n, BS), dim3(BS), 0, st, R, n, (const uint32_t*)flag, (const uint32_t*)pos, nt,
+                     dt, dr);
+  LAUNCH_CHECK();
+  std::vector<uint32_t> t(nt), order(nt);
+  std::vector<uint8_t> r(nt * 32);
+  HIPCHK(hipMemcpyAsync(t.data(), dt, nt * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(r.data(), dr, nt * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nt; ++i) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t[a] < t[b]; });
+  for (uint64_t i = 0; i < nt; ++i) {
+    h_tries[i] = t[order[i]];
+    memcpy(h_roots32 + 32 * i, r.data() + 32ull * order[i], 32);
+  }
+  return KH_OK;
+}
+
+// drop whole tries: their live records listed (a scan: record order), out of the map, dead
+static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t* n_evicted) {
+  if (!h->sps.empty()) throw KhError{KH_EINVAL, "kh_forest_evict: a savepoint is open"};
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  *n_evicted = 0;
+  const uint64_t n = h->rn;
+  if (k == 0 || n == 0 || h->mcap == 0) return;
+  if (k >= (1ULL << 31)) throw KhError{KH_EINVAL, "trie list too large"};
+  std::vector<uint32_t> ids(tries, tries + k);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  const uint64_t nt = ids.size();
+  Layout L;
+  uint32_t *dt, *flag, *pos, *list;
+  unsigned long long* tot;
+  char* scr;
+  L.add(dt, nt);
+  L.add_all(n, flag, pos, list);
+  L.add(scr, scan_scratch_bytes(n + 1, 4));
+  L.add(tot, 8);
+  place(h->gbuf, L);
+  const Recs R = recs_of(h);
+  HIPCHK(hipMemcpyAsync(dt, ids.data(), nt * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
+  hipLaunchKernelGGL(k_evict_flags, GRID(n, BS), dim3(BS), 0, st, R, n, (const uint32_t*)dt, (uint32_t)nt, flag,
+                     tot + 1);
+  LAUNCH_CHECK();
+  scan_exclusive<uint32_t>(flag, pos, n, (uint32_t*)tot, scr, st);
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // (ids is a host temporary)
+  const uint64_t nl = (uint32_t)c->h_pinned[0], nkeys = c->h_pinned[1], ntries = c->h_pinned[2];
+  if (nl == 0) return;
+  ++h->epoch;
+  hipLaunchKernelGGL(k_evict_list, GRID(n, BS), dim3(BS), 0, st, n, (const uint32_t*)flag, (const uint32_t*)pos, nl,
+                     list);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_map_delete, GRID(nl, BS), dim3(BS), 0, st, map_of(h), R, (const uint32_t*)list, nl,
+                     (const uint32_t*)nullptr, (uint64_t)0, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p,
+                     (uint64_t*)nullptr);
+  LAUNCH_CHECK();
+  HIPCHK(hipStreamSynchronize(st));
+  h->rdead += nl;
+  h->nleaves -= nkeys;
+  *n_evicted = ntries;
+}
+
 extern "C" {
+
+int kh_forest_load_nodes(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
+                         const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
+                         uint64_t* n_missing, kh_stats* stats) {
+  if (n_missing) *n_missing = 0;
+  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
+  if ((k && (!tries || !roots32)) || (n && (!d_enc || !d_off)) || (miss_cap && (!miss_idx || !miss32)))
+    return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(f);
+    HIPCHK(hipSetDevice(f->c->dev));
+    forest_load(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats);
+  })
+}
+
+int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                              const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32,
+                              uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
+  if (n_missing) *n_missing = 0;
+  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
+  if ((k && (!tries || !roots32)) || (n && !off) || (miss_cap && (!miss_idx || !miss32)))
+    return set_err(KH_EINVAL, "null buffer");
+  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
+  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(f);
+    kh_ctx* c = f->c;
+    HIPCHK(hipSetDevice(c->dev));
+    const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
+    c->in_vals.ensure(bytes + 64);
+    c->in_voff.ensure((n + 1) * 8 + 64);
+    std::vector<uint64_t> rel(n + 1, 0);
+    for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
+    if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    forest_load(f, tries, roots32, k, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, miss_idx, miss32,
+                miss_cap, n_missing, stats);
+  })
+}
+
+int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries) {
+  if (!f || !f->forest || !n_tries) return set_err(KH_EINVAL, "null handle or output, or not a forest");
+  API_TRY({
+    HANDLE_LOCK(f);
+    HIPCHK(hipSetDevice(f->c->dev));
+    return forest_roots(f, h_tries, h_roots32, cap, n_tries);
+  })
+}
+
+int kh_forest_evict(kh_trie* f, const uint32_t* tries, uint64_t k, uint64_t* n_evicted) {
+  uint64_t dropped = 0;
+  if (n_evicted) *n_evicted = 0;
+  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
+  if (k && !tries) return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(f);
+    HIPCHK(hipSetDevice(f->c->dev));
+    forest_evict(f, tries, k, &dropped);
+    if (n_evicted) *n_evicted = dropped;
+  })
+}
 
 int kh_trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n, uint32_t flags,
                   uint8_t* found, uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off,

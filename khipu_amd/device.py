@@ -598,6 +598,83 @@ class ResidentForest(_Versioned):
                                     ctypes.byref(st)))
         return {int(tries[i]): roots[32 * i:32 * i + 32].tobytes() for i in range(nt.value)}
 
+    @classmethod
+    def from_nodes(cls, ctx, roots, nodes, hash_keys=False, emit=False):
+        """A forest resumed from {trie_id: root} and a node store {hash: encoding} (what
+        checkpoint() returns): kh_forest_open then load_nodes."""
+        f = cls(ctx, hash_keys=hash_keys, emit=emit)
+        f.load_nodes(roots, nodes)
+        return f
+
+    def load_nodes_raw(self, ids, roots, encs, miss_cap=None):
+        """One kh_forest_load_nodes call: (rc, n_missing, [(list index, hash)] written)."""
+        ids, roots, encs = list(ids), list(roots), list(encs)
+        k = len(ids)
+        tb = np.asarray(ids + [0], np.uint32)
+        rb = np.frombuffer(b"".join(bytes(r) for r in roots) + b"\0", np.uint8).copy()
+        ed, eo = _pack_dev(encs, self.dev)
+        cap = k if miss_cap is None else miss_cap
+        mi = np.zeros(max(cap, 1), np.uint32)
+        mh = np.zeros(32 * max(cap, 1), np.uint8)
+        nm = ctypes.c_uint64(0)
+        self.ctx._sync()
+        rc = lib().kh_forest_load_nodes(self.h, tb.ctypes.data, rb.ctypes.data, k, _ptr(ed), _ptr(eo), len(encs),
+                                        mi.ctypes.data, mh.ctypes.data, cap, ctypes.byref(nm), None)
+        w = min(int(nm.value), cap)
+        return rc, int(nm.value), [(int(mi[e]), mh[32 * e:32 * e + 32].tobytes()) for e in range(w)]
+
+    def load_nodes(self, roots, nodes):
+        """Page tries in (kh_forest_load_nodes): roots {trie_id: root}, nodes {hash: encoding} or a
+        list of encodings.  All or nothing.  Nodes missing from the store raise
+        MPTNodeMissingException with .missing = [(trie_id, hash)]: every missing reference of the
+        first round of the walk that lacks one."""
+        ids = list(roots)
+        encs = list(nodes.values()) if isinstance(nodes, dict) else list(nodes)
+        cap = max(len(ids), 16)
+        for _ in range(2):
+            rc, nm, miss = self.load_nodes_raw(ids, [roots[t] for t in ids], encs, cap)
+            if rc == _lib.KH_ENODE and nm > cap:
+                cap = nm
+                continue
+            if rc == _lib.KH_ENODE:
+                e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+                e.missing = [(ids[j], h) for j, h in miss]
+                raise e
+            check(rc)
+            return
+        raise RuntimeError("kh_forest_load_nodes: size negotiation failed")
+
+    def roots(self):
+        """{trie_id: root} of every trie the forest holds (kh_forest_roots)."""
+        n = ctypes.c_uint64()
+        cap = 0
+        for _ in range(3):
+            tries = np.zeros(max(cap, 1), np.uint32)
+            roots = np.zeros(32 * max(cap, 1), np.uint8)
+            self.ctx._sync()
+            rc = lib().kh_forest_roots(self.h, tries.ctypes.data, roots.ctypes.data, cap, ctypes.byref(n))
+            if rc == _lib.KH_ENOSPC:
+                cap = n.value
+                continue
+            check(rc)
+            return {int(tries[i]): roots[32 * i:32 * i + 32].tobytes() for i in range(n.value)}
+        raise RuntimeError("kh_forest_roots: size negotiation failed")
+
+    def evict(self, ids):
+        """Drop whole tries from HBM (kh_forest_evict); returns the number dropped.  An evicted id
+        reads as an empty trie until it is loaded again."""
+        ids = list(ids)
+        tb = np.asarray(ids + [0], np.uint32)
+        n = ctypes.c_uint64()
+        self.ctx._sync()
+        check(lib().kh_forest_evict(self.h, tb.ctypes.data, len(ids), ctypes.byref(n)))
+        return int(n.value)
+
+    def checkpoint(self, verify=False):
+        """({trie_id: root}, {hash: encoding}): the resumable state of the current version, what
+        from_nodes / load_nodes take."""
+        return self.roots(), dict(self.export_nodes(verify=verify))
+
     def nodes(self):
         return emitted_nodes(lambda *a: lib().kh_trie_emit_nodes(self.h, *a))
 
