@@ -31,6 +31,13 @@
  *                           into a resident forest by (trie id, storage root), or a whole forest
  *                           resumed from a checkpoint; kh_forest_roots lists what is resident,
  *                           kh_forest_evict drops cold tries again
+ *   kh_trie_open_partial    the lazy getNode of MerklePatriciaTrie(rootHash, source)
+ *                           (MerklePatriciaTrie.scala:60-66,520-542): a trie opened from the nodes at
+ *                           hand (a block's witness), the subtrees it lacks kept as stubs; a commit
+ *                           that needs one returns KH_ENODE where the reference throws
+ *                           MPTNodeMissingException, kh_trie_missing names the hashes and
+ *                           kh_trie_fill_nodes takes the fetched nodes (kh_forest_load_partial: the
+ *                           same for many storage tries)
  *   kh_trie_prove           the nodes MerklePatriciaTrie.get visits (MerklePatriciaTrie.scala:90-147)
  *                           for a batch of keys: an eth_getProof answer, or a block's witness
  *   kh_verify_proofs        that walk re-done from a root over the listed nodes alone
@@ -367,6 +374,88 @@ int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* 
                               const uint8_t* enc, const uint64_t* off, uint64_t n,
                               uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing,
                               kh_stats* stats);
+/* ---- partial handles: open from a witness, commit along the resident paths, fill what is missing
+ * MerklePatriciaTrie(rootHash, source) loads a node only when a get, put or remove walks into it
+ * (MerklePatriciaTrie.scala:60-66,520-542) and throws MPTNodeMissingException for a node its source
+ * lacks; the caller fetches that node and retries.  Here a handle may hold a trie PARTLY: a
+ * subtree whose node is absent from the store it was opened from is kept as a STUB, a record that
+ * stands for the subtree and remembers the reference its parent holds and the hash of the node to
+ * fetch.  An extension whose branch is absent is one stub with its branch: the stub still stands
+ * for the extension (it is exported, proved and served by hash) and asks for the branch.  An
+ * embedded node (< 32 B) is part of its parent and never a stub; a trie's root node is never a stub.
+ *
+ * kh_trie_open_partial / kh_forest_load_partial take the arguments and argument checks of
+ * kh_trie_open_nodes / kh_forest_load_nodes and differ in this: a hash reference below a root that
+ * is absent from the store makes a stub instead of ending the round.  A missing ROOT is still
+ * KH_ENODE, reported as there, and nothing is loaded for any listed trie.  All or nothing, the
+ * fixed record order, the journaling under a savepoint and the end of export cursors carry over.
+ * kh_trie_size counts the keys the handle holds (leaves and value-only branches);
+ * kh_trie_stubs the live stubs, exactly.  A handle without stubs behaves in every call as one
+ * opened in full.
+ *
+ * Commits (kh_trie_apply, kh_forest_apply, kh_block_commit, kh_trie_root_of and their _host forms)
+ * on a handle with stubs:
+ *   - an untouched stub under a branch the commit opens is carried as it is: its parent's new
+ *     encoding holds the reference the stub keeps.  So a put into an empty slot of a branch whose
+ *     other children are all stubs commits with no fetch;
+ *   - an op whose walk reaches a stub, and a delete that leaves a stub as its parent's only child
+ *     (the reference's fix loads that child, MerklePatriciaTrie.scala:430-477), need a missing
+ *     node: the commit returns KH_ENODE and the handle is exactly as before -- root, values, last
+ *     roots, write-back set and export bytes.  Every stub any op of the batch reached is reported
+ *     by that one refusal (the collapsing ones are found, and reported, only once no op reaches a
+ *     stub any more);
+ *   - an op that leaves the path inside an extension whose branch is a stub does not need the
+ *     branch, as in the reference: the extension is split over the branch's hash;
+ *   - a successful commit never creates or removes a stub, and moves none but this one: a stub
+ *     that stands for the branch under an extension the store did hold is re-anchored when that
+ *     extension is split or its parent collapses -- the extension is re-cut over the branch's
+ *     hash, which is all the reference's put and fix read of it.
+ * kh_trie_missing: the distinct (trie id, hash to fetch) pairs of the most recent commit, block
+ * commit or root_of on the handle (trie id 0 on a single trie); empty unless that call returned
+ * KH_ENODE for missing nodes; order unspecified; KH_ENOSPC with *n when cap is short (with cap 0,
+ * the size query, kh_last_error keeps the refused commit's message).  After a block commit each of
+ * the two handles holds its own list.
+ *
+ * kh_trie_fill_nodes: the live stubs whose node is in the store (the store layout of
+ * kh_trie_open_nodes) are resolved, in the load's rounds; the children a resolved node refers to
+ * and the store lacks become stubs in turn, nodes no stub names are ignored.  All or nothing: a
+ * malformed node is KH_EINVAL and the handle is as before.  KH_EINVAL while a savepoint is open
+ * (as kh_trie_compact).  Ends export cursors.  *n_decoded (nullable) = the store nodes decoded
+ * into the handle.
+ *
+ * Reads: kh_trie_get gives found = KH_FOUND_UNKNOWN (empty value) for a key whose walk reaches a
+ * stub, and so does kh_trie_prove, whose proof for such a key is the resident nodes of the path
+ * (kh_verify_proofs calls it KH_PROOF_SHORT); kh_trie_need_host returns per key the hash of the
+ * stub its walk reaches (need_flag 1, need32[32i..)) or need_flag 0 -- what to fetch before a
+ * commit of those keys, the collapse case apart.  kh_trie_export_nodes skips stubs (a branch
+ * encodes a stub child by the reference the stub keeps): the export of a partial handle is the
+ * witness it holds.  kh_trie_nodes_by_hash never answers from a stub.  To kh_forest_roots,
+ * kh_forest_evict, kh_trie_compact, kh_trie_copy, savepoints and rollbacks a stub is a live record
+ * of its trie.
+ * kh_trie_open_partial with ctx NULL opens on the context the _host entry points share, as
+ * kh_forest_open does (the store then lies in HBM of the current device). */
+#define KH_FOUND_UNKNOWN 2
+int kh_trie_open_partial(kh_ctx* ctx, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                         uint32_t flags, uint8_t missing32[32], kh_trie** out);
+int kh_trie_open_partial_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
+                              uint32_t flags, uint8_t missing32[32], kh_trie** out);
+int kh_forest_load_partial(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                           const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                           uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing,
+                           kh_stats* stats);
+int kh_forest_load_partial_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                                const uint8_t* enc, const uint64_t* off, uint64_t n,
+                                uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing,
+                                kh_stats* stats);
+int kh_trie_fill_nodes(kh_trie* h, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n, uint64_t* n_decoded,
+                       kh_stats* stats);
+int kh_trie_fill_nodes_host(kh_trie* h, const uint8_t* enc, const uint64_t* off, uint64_t n, uint64_t* n_decoded,
+                            kh_stats* stats);
+int kh_trie_stubs(const kh_trie* h, uint64_t* n);
+int kh_trie_missing(const kh_trie* h, uint32_t* tries, uint8_t* hashes32, uint64_t cap, uint64_t* n);
+int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
+                      uint8_t* need_flag, uint8_t* need32);
+
 /* Every trie the forest holds (>= 1 key), ascending ids, with its root: one streaming pass over
  * the records, read-only on the handle.  KH_ENOSPC with *n_tries when cap is short. */
 int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries);

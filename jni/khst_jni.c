@@ -81,6 +81,29 @@ static void throw_kh_hash(JNIEnv* env, int rc, const uint8_t* missing32) {
             kh_last_error());
 }
 static void throw_kh(JNIEnv* env, int rc) { throw_kh_hash(env, rc, NULL); }
+/* a refused commit: KH_ENODE carries the first hash of a's missing list, or of b's (kh_trie_missing:
+ * a partial handle whose commit walked into a stub; missing() lists them all) */
+static void throw_kh_commit(JNIEnv* env, int rc, kh_trie* a, kh_trie* b) {
+  if (rc == KH_ENODE) {
+    kh_trie* hs[2] = {a, b};
+    for (int i = 0; i < 2; ++i) {
+      uint64_t n = 0;
+      if (!hs[i] || kh_trie_missing(hs[i], NULL, NULL, 0, &n) != KH_ENOSPC || !n) continue;
+      uint32_t* t = malloc(4 * (size_t)n);
+      uint8_t* h = malloc(32 * (size_t)n);
+      const int got = t && h && kh_trie_missing(hs[i], t, h, n, &n) == KH_OK && n;
+      uint8_t first[32];
+      if (got) memcpy(first, h, 32);
+      free(t);
+      free(h);
+      if (got) { /* (the size query leaves kh_last_error alone: the commit's message is thrown) */
+        throw_node_missing(env, first);
+        return;
+      }
+    }
+  }
+  throw_kh(env, rc);
+}
 
 /* ---- host copies of Java arrays (no critical regions) ----
  * A Bufs holds every buffer one wrapper call allocates; bufs_free releases them all.  An input
@@ -656,7 +679,7 @@ JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_apply(JNIEnv* env, jclass 
   const int rc = kh_trie_apply_host(H(handle), k, v, o, nup, d, ndel, (uint32_t)klen, (uint32_t)flags, root, &st);
   bufs_free(&b);
   if (rc != KH_OK) {
-    throw_kh(env, rc);
+    throw_kh_commit(env, rc, H(handle), NULL);
     return NULL;
   }
   put_stats(env, statsOut, &st);
@@ -704,7 +727,7 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_forestApply(JNIEnv* env, jclass
   bufs_free(&b);
   if (rc == KH_ENOSPC) return -(jlong)nt; /* committed; kh_forest_last_roots reads them again */
   if (rc != KH_OK) {
-    throw_kh(env, rc);
+    throw_kh_commit(env, rc, H(handle), NULL);
     return 0;
   }
   return (jlong)nt;
@@ -744,7 +767,7 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_forestLastRoots(JNIEnv* env, jc
  * (device addresses of the encodings and the n + 1 offsets, on the forest's context). */
 static void forest_load(JNIEnv* env, jlong handle, jintArray tries, jbyteArray roots, jbyteArray enc, jlongArray off,
                         jlong dEnc, jlong dOff, jlong dN, jintArray missIdxOut, jbyteArray missOut,
-                        jlongArray nMissingOut) {
+                        jlongArray nMissingOut, int partial) {
   const uint64_t k = (uint64_t)len_of(env, tries);
   const jsize icap = len_of(env, missIdxOut), hcap = len_of(env, missOut) / 32;
   const uint64_t cap = (uint64_t)(icap < hcap ? icap : hcap);
@@ -763,9 +786,15 @@ static void forest_load(JNIEnv* env, jlong handle, jintArray tries, jbyteArray r
     return;
   }
   if (cap) memset(mh, 0, 32);
-  const int rc = dEnc ? kh_forest_load_nodes(H(handle), t, r, k, (const uint8_t*)(intptr_t)dEnc,
-                                             (const uint64_t*)(intptr_t)dOff, (uint64_t)dN, mi, mh, cap, &nm, NULL)
-                      : kh_forest_load_nodes_host(H(handle), t, r, k, e, o, count_of(env, off), mi, mh, cap, &nm, NULL);
+  int rc;
+  if (partial)
+    rc = dEnc ? kh_forest_load_partial(H(handle), t, r, k, (const uint8_t*)(intptr_t)dEnc,
+                                       (const uint64_t*)(intptr_t)dOff, (uint64_t)dN, mi, mh, cap, &nm, NULL)
+              : kh_forest_load_partial_host(H(handle), t, r, k, e, o, count_of(env, off), mi, mh, cap, &nm, NULL);
+  else
+    rc = dEnc ? kh_forest_load_nodes(H(handle), t, r, k, (const uint8_t*)(intptr_t)dEnc,
+                                     (const uint64_t*)(intptr_t)dOff, (uint64_t)dN, mi, mh, cap, &nm, NULL)
+              : kh_forest_load_nodes_host(H(handle), t, r, k, e, o, count_of(env, off), mi, mh, cap, &nm, NULL);
   if (rc == KH_ENODE) {
     const uint64_t w = nm < cap ? nm : cap;
     const jlong n64 = (jlong)nm;
@@ -781,7 +810,7 @@ JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadNodes(JNIEnv* env, jcl
                                                                jintArray missIdxOut, jbyteArray missOut,
                                                                jlongArray nMissingOut) {
   (void)cls;
-  forest_load(env, handle, tries, roots, enc, off, 0, 0, 0, missIdxOut, missOut, nMissingOut);
+  forest_load(env, handle, tries, roots, enc, off, 0, 0, 0, missIdxOut, missOut, nMissingOut, 0);
 }
 JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadNodesDevice(JNIEnv* env, jclass cls, jlong handle,
                                                                      jintArray tries, jbyteArray roots, jlong dEnc,
@@ -792,7 +821,184 @@ JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadNodesDevice(JNIEnv* en
     throw_cls(env, "java/lang/IllegalArgumentException", "dEnc / dOff: device addresses");
     return;
   }
-  forest_load(env, handle, tries, roots, NULL, NULL, dEnc, dOff, n, missIdxOut, missOut, nMissingOut);
+  forest_load(env, handle, tries, roots, NULL, NULL, dEnc, dOff, n, missIdxOut, missOut, nMissingOut, 0);
+}
+
+/* ---- partial handles: open from a witness, fill what a commit misses ----
+ * The lazy getNode of MerklePatriciaTrie(rootHash, source) (MerklePatriciaTrie.scala:60-66,
+ * 520-542): the subtrees whose node the store lacks stay stubs; only a missing ROOT throws
+ * MPTNodeMissingException here.  A commit that walks into a stub throws it too (apply /
+ * blockCommit / rootOf, KH_ENODE); missing(handle) then lists what to fetch and fillNodes takes
+ * the fetched nodes (the fetch-and-retry loop). */
+JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadPartial(JNIEnv* env, jclass cls, jlong handle,
+                                                                 jintArray tries, jbyteArray roots, jbyteArray enc,
+                                                                 jlongArray off, jintArray missIdxOut,
+                                                                 jbyteArray missOut, jlongArray nMissingOut) {
+  (void)cls;
+  forest_load(env, handle, tries, roots, enc, off, 0, 0, 0, missIdxOut, missOut, nMissingOut, 1);
+}
+JNIEXPORT void JNICALL Java_khipu_trie_gpu_Khst_forestLoadPartialDevice(JNIEnv* env, jclass cls, jlong handle,
+                                                                       jintArray tries, jbyteArray roots, jlong dEnc,
+                                                                       jlong dOff, jlong n, jintArray missIdxOut,
+                                                                       jbyteArray missOut, jlongArray nMissingOut) {
+  (void)cls;
+  if (!dEnc || !dOff) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "dEnc / dOff: device addresses");
+    return;
+  }
+  forest_load(env, handle, tries, roots, NULL, NULL, dEnc, dOff, n, missIdxOut, missOut, nMissingOut, 1);
+}
+/* open a single trie from the nodes at hand (as openNodes; dEnc != 0: the store is in HBM, device
+ * addresses on the shared context of the current device) */
+static jlong open_partial(JNIEnv* env, jbyteArray root32, jbyteArray enc, jlongArray off, jlong dEnc, jlong dOff,
+                          jlong dN, jint flags, jbyteArray missingOut) {
+  uint8_t missing[32] = {0};
+  kh_trie* h = NULL;
+  Bufs b = {0};
+  const uint8_t* r = in_b(env, &b, root32);
+  const uint8_t* e = dEnc ? NULL : in_b(env, &b, enc);
+  const uint64_t* o = dEnc ? NULL : in_l(env, &b, off);
+  if (bufs_failed(env, &b)) return 0;
+  if (!r || len_of(env, root32) < 32) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "root32: 32 bytes");
+    return 0;
+  }
+  const int rc = dEnc ? kh_trie_open_partial(NULL, r, (const uint8_t*)(intptr_t)dEnc, (const uint64_t*)(intptr_t)dOff,
+                                             (uint64_t)dN, (uint32_t)flags, missing, &h)
+                      : kh_trie_open_partial_host(r, e, o, count_of(env, off), (uint32_t)flags, missing, &h);
+  bufs_free(&b);
+  if (rc == KH_ENODE) put_b(env, missingOut, missing, 32);
+  if (rc != KH_OK) {
+    throw_kh_hash(env, rc, missing);
+    return 0;
+  }
+  return (jlong)(intptr_t)h;
+}
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_openPartial(JNIEnv* env, jclass cls, jbyteArray root32,
+                                                            jbyteArray enc, jlongArray off, jint flags,
+                                                            jbyteArray missingOut) {
+  (void)cls;
+  return open_partial(env, root32, enc, off, 0, 0, 0, flags, missingOut);
+}
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_openPartialDevice(JNIEnv* env, jclass cls, jbyteArray root32,
+                                                                  jlong dEnc, jlong dOff, jlong n, jint flags,
+                                                                  jbyteArray missingOut) {
+  (void)cls;
+  if (!dEnc || !dOff) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "dEnc / dOff: device addresses");
+    return 0;
+  }
+  return open_partial(env, root32, NULL, NULL, dEnc, dOff, n, flags, missingOut);
+}
+/* resolve the stubs whose node is in the store (between commits: no savepoint open); returns the
+ * number of store nodes decoded into the handle */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_fillNodes(JNIEnv* env, jclass cls, jlong handle, jbyteArray enc,
+                                                          jlongArray off) {
+  (void)cls;
+  uint64_t nd = 0;
+  Bufs b = {0};
+  const uint8_t* e = in_b(env, &b, enc);
+  const uint64_t* o = in_l(env, &b, off);
+  if (bufs_failed(env, &b)) return 0;
+  const int rc = kh_trie_fill_nodes_host(H(handle), e, o, count_of(env, off), &nd, NULL);
+  bufs_free(&b);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)nd;
+}
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_fillNodesDevice(JNIEnv* env, jclass cls, jlong handle, jlong dEnc,
+                                                                jlong dOff, jlong n) {
+  (void)cls;
+  uint64_t nd = 0;
+  if (!dEnc || !dOff) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "dEnc / dOff: device addresses");
+    return 0;
+  }
+  const int rc = kh_trie_fill_nodes(H(handle), (const uint8_t*)(intptr_t)dEnc, (const uint64_t*)(intptr_t)dOff,
+                                    (uint64_t)n, &nd, NULL);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)nd;
+}
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_stubs(JNIEnv* env, jclass cls, jlong handle) {
+  (void)cls;
+  uint64_t n = 0;
+  const int rc = kh_trie_stubs(H(handle), &n);
+  if (rc != KH_OK) throw_kh(env, rc);
+  return (jlong)n;
+}
+/* what the last commit, block commit or rootOf on the handle needed and the handle lacks: 36
+ * bytes an entry, the trie id (4 bytes, little endian; 0 on a single trie) then the hash to
+ * fetch -- the hash MPTNodeMissingException carries in the reference.  Empty unless that call
+ * threw it.  The count is negotiated as forestRoots does. */
+JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_missing(JNIEnv* env, jclass cls, jlong handle) {
+  (void)cls;
+  uint64_t nm = 0, cap = 0;
+  uint32_t* t = NULL;
+  uint8_t* r = NULL;
+  int rc = KH_ENOSPC;
+  for (int tries = 0; rc == KH_ENOSPC && tries < 16; ++tries) { /* the first call reports the count */
+    rc = kh_trie_missing(H(handle), t, r, cap, &nm);
+    if (rc == KH_ENOSPC) {
+      free(t);
+      free(r);
+      cap = nm + nm / 8;
+      t = malloc(4 * (size_t)(cap ? cap : 1));
+      r = malloc(32 * (size_t)(cap ? cap : 1));
+      if (!t || !r) rc = KH_ENOMEM;
+    }
+  }
+  jbyteArray out = NULL;
+  uint8_t* packed = rc == KH_OK ? malloc(36 * (size_t)(nm ? nm : 1)) : NULL;
+  if (rc == KH_OK && !packed) rc = KH_ENOMEM;
+  if (rc == KH_OK) {
+    for (uint64_t i = 0; i < nm; ++i) {
+      for (int q = 0; q < 4; ++q) packed[36 * i + q] = (uint8_t)(t[i] >> (8 * q));
+      memcpy(packed + 36 * i + 4, r + 32 * i, 32);
+    }
+    out = bytes_of(env, packed, (jsize)(36 * nm));
+  }
+  free(packed);
+  free(t);
+  free(r);
+  if (rc != KH_OK) throw_kh(env, rc);
+  return out;
+}
+/* per key (klen bytes each; tries nullable on a single trie) 33 bytes: 1 and the hash of the node
+ * to fetch when the key's walk reaches a stub, else 33 zero bytes */
+JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_need(JNIEnv* env, jclass cls, jlong handle, jintArray tries,
+                                                          jbyteArray keys, jint klen) {
+  (void)cls;
+  const uint64_t n = klen > 0 ? (uint64_t)(len_of(env, keys) / klen) : 0;
+  Bufs b = {0};
+  const uint32_t* t = in_i(env, &b, tries);
+  const uint8_t* k = in_b(env, &b, keys);
+  uint8_t* fl = bufs_alloc(&b, (size_t)(n ? n : 1));
+  uint8_t* hs = bufs_alloc(&b, 32 * (size_t)(n ? n : 1));
+  uint8_t* packed = bufs_alloc(&b, 33 * (size_t)(n ? n : 1));
+  if (bufs_failed(env, &b)) return NULL;
+  if (tries && (uint64_t)len_of(env, tries) < n) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "tries: one id per key");
+    return NULL;
+  }
+  const int rc = kh_trie_need_host(H(handle), t, k, (uint32_t)klen, n, fl, hs);
+  jbyteArray out = NULL;
+  if (rc == KH_OK) {
+    for (uint64_t i = 0; i < n; ++i) {
+      packed[33 * i] = fl[i];
+      memcpy(packed + 33 * i + 1, hs + 32 * i, 32);
+    }
+    out = bytes_of(env, packed, (jsize)(33 * n));
+  }
+  bufs_free(&b);
+  if (rc != KH_OK) throw_kh(env, rc);
+  return out;
 }
 
 /* every trie the forest holds, ascending ids: 36 bytes a trie, the id (4 bytes, little endian)
@@ -882,7 +1088,7 @@ JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_blockCommit(
                                       &st);
   bufs_free(&b);
   if (rc != KH_OK) {
-    throw_kh(env, rc);
+    throw_kh_commit(env, rc, H(storage), H(state));
     return NULL;
   }
   put_stats(env, statsOut, &st);
@@ -1214,7 +1420,7 @@ JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_rootOf(JNIEnv* env, jclass
   const int rc = kh_trie_root_of_host(H(handle), k, v, o, nup, d, ndel, (uint32_t)klen, (uint32_t)flags, root, NULL);
   bufs_free(&b);
   if (rc != KH_OK) {
-    throw_kh(env, rc);
+    throw_kh_commit(env, rc, H(handle), NULL);
     return NULL;
   }
   return bytes_of(env, root, 32);

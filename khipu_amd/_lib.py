@@ -22,6 +22,7 @@ KH_EMIT_NODES = 0x2
 KH_SHARD_RCCL = 0x4  # kh_trie_root_sharded: the RCCL exchange even when a device repeats (tests' loopback)
 KH_NO_TRIE = 0xFFFFFFFF
 KH_EXPORT_VERIFY = 0x1  # kh_trie_export_nodes: re-hash every encoding against its cached reference
+KH_FOUND_UNKNOWN = 2  # kh_trie_get / kh_trie_prove: the key's walk reaches a stub of a partial handle
 KH_PROVE_SHARED = 0x1  # kh_trie_prove: every (record, node) once in the table (a block witness)
 # kh_verify_proofs statuses
 KH_PROOF_ABSENT = 0     # valid: the key is not in the trie
@@ -45,7 +46,9 @@ EXPORTS = (
     "kh_trie_release", "kh_trie_savepoint_depth", "kh_trie_root_of", "kh_trie_root_of_host", "kh_trie_copy",
     "kh_verify_nodes_packed", "kh_trie_usage", "kh_trie_compact", "kh_trie_export_nodes", "kh_trie_nodes_by_hash",
     "kh_trie_prove", "kh_verify_proofs", "kh_forest_load_nodes", "kh_forest_load_nodes_host", "kh_forest_roots",
-    "kh_forest_evict",
+    "kh_forest_evict", "kh_trie_open_partial", "kh_trie_open_partial_host", "kh_forest_load_partial",
+    "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
+    "kh_trie_missing", "kh_trie_need_host",
 )
 
 
@@ -180,6 +183,15 @@ def lib():
     L.kh_forest_load_nodes_host.argtypes = L.kh_forest_load_nodes.argtypes
     L.kh_forest_roots.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.kh_forest_evict.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.kh_trie_open_partial.argtypes = L.kh_trie_open_nodes.argtypes
+    L.kh_trie_open_partial_host.argtypes = L.kh_trie_open_nodes_host.argtypes
+    L.kh_forest_load_partial.argtypes = L.kh_forest_load_nodes.argtypes
+    L.kh_forest_load_partial_host.argtypes = L.kh_forest_load_nodes.argtypes
+    L.kh_trie_fill_nodes.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp]
+    L.kh_trie_fill_nodes_host.argtypes = L.kh_trie_fill_nodes.argtypes
+    L.kh_trie_stubs.argtypes = [vp, ctypes.POINTER(u64)]
+    L.kh_trie_missing.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
+    L.kh_trie_need_host.argtypes = [vp, vp, vp, u32, u64, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

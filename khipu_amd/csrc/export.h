@@ -32,13 +32,20 @@ constexpr uint64_t EXP_NO_HIT = ~0ULL;            // by-hash: hit = 2 * record +
 
 KH_HD bool exp_has_lower(uint32_t d, uint32_t db) { return db != EL_LEAF && d < db; }
 // a node written as a list of 17 items: a branch (a value-only branch is written by vb_encode)
-KH_HD bool exp_is_branch(uint32_t db) { return db != EL_LEAF && db != VB_DEPTH; }
+// A stub (forest.h EL_STUB) stands for a node the handle does not hold: it is never selected and
+// never answers by hash, except for the extension it still holds above a missing branch (rmask >
+// d), which is its upper node; as a child it gives its parent the reference it keeps, rref, like
+// any other record.  exp_db: the depth at which a record's lower node starts.
+KH_HD bool exp_is_branch(uint32_t db) { return db != EL_LEAF && db != VB_DEPTH && db != EL_STUB; }
+KH_HD uint32_t exp_db(const Recs& R, uint64_t r) { return R.rdb[r] == EL_STUB ? (R.rmask[r] & 0xFFu) : R.rdb[r]; }
 
 // the nodes of record r a node store needs (trie filter applied)
 KH_HD uint32_t exp_select(const Recs& R, uint64_t r, uint32_t filter) {
   if (R.rlive[r] != REC_LIVE) return 0;
   if (filter != EXP_ALL_TRIES && R.rt[r] != filter) return 0;
   const uint32_t d = R.rd[r], db = R.rdb[r];
+  if (db == EL_STUB)  // the subtree is not held; the extension above a missing branch is
+    return (exp_db(R, r) > d && (R.rrl[r] == 32 || d == 0)) ? EXP_UPPER : 0;
   uint32_t sel = (R.rrl[r] == 32 || d == 0) ? EXP_UPPER : 0;
   if (exp_has_lower(d, db) && R.rbrl[r] == 32) sel |= EXP_LOWER;
   return sel;
@@ -81,7 +88,7 @@ KH_HD uint32_t exp_lower_len(const Recs& R, const uint8_t* heap, uint64_t r, uin
   return R.rdb[r] == VB_DEPTH ? exp_list_len(16 + exp_value_item_len(R, heap, r)) : exp_branch_len(S);
 }
 KH_HD uint32_t exp_upper_len(const Recs& R, const uint8_t* heap, uint64_t r, uint32_t S) {
-  const uint32_t d = R.rd[r], db = R.rdb[r];
+  const uint32_t d = R.rd[r], db = exp_db(R, r);
   if (db == EL_LEAF) return exp_list_len(exp_hp_item_len(64 - d) + exp_value_item_len(R, heap, r));
   if (d < db) {
     const uint32_t brl = R.rbrl[r];
@@ -156,7 +163,7 @@ KH_HD void exp_write_valued(const Recs& R, const uint8_t* heap, uint64_t r, uint
 }
 // the extension above a branch (lane 0)
 KH_HD void exp_write_ext(const Recs& R, uint64_t r, uint8_t* out) {
-  const uint32_t d = R.rd[r], db = R.rdb[r], brl = R.rbrl[r];
+  const uint32_t d = R.rd[r], db = exp_db(R, r), brl = R.rbrl[r];
   const uint32_t payload = exp_hp_item_len(db - d) + (brl == 32 ? 33 : brl);
   uint32_t p = vb_put_len(out, 0, payload, 0xC0);
   p = exp_put_hp((const uint8_t*)R.key(r), d, db, false, out, p);
@@ -168,7 +175,7 @@ KH_HD void exp_write_ext(const Recs& R, uint64_t r, uint8_t* out) {
 // through len[2] the lengths written (0: not selected)
 KH_HD void exp_write(const Recs& R, const uint8_t* heap, uint64_t r, uint32_t sel, uint32_t lane, uint32_t child,
                      uint32_t pre, uint32_t S, uint8_t* out, uint32_t len[2]) {
-  const uint32_t d = R.rd[r], db = R.rdb[r];
+  const uint32_t d = R.rd[r], db = exp_db(R, r);  // (a stub is selected for its extension only: d < db)
   len[0] = len[1] = 0;
   if (sel & EXP_UPPER) {
     len[0] = exp_upper_len(R, heap, r, S);
@@ -227,12 +234,14 @@ KH_HD void exp_scan_record(const Recs& R, uint64_t r, const uint64_t* tags, cons
                            const uint64_t* Q, uint64_t* hits) {
   if (R.rlive[r] != REC_LIVE) return;
   const uint32_t d = R.rd[r], db = R.rdb[r];
+  const bool stub = db == EL_STUB;  // it answers for the extension it holds, never for the missing node
+  if (stub && exp_db(R, r) <= d) return;
   uint64_t w[4];
   if (R.rrl[r] == 32) {
     for (int q = 0; q < 4; ++q) w[q] = R.rref[4 * r + q];
     exp_table_match(tags, qidx, mask, Q, w, 2 * r, hits);
   }
-  if (exp_has_lower(d, db) && R.rbrl[r] == 32) {
+  if (!stub && exp_has_lower(d, db) && R.rbrl[r] == 32) {
     for (int q = 0; q < 4; ++q) w[q] = R.rbref[4 * r + q];
     exp_table_match(tags, qidx, mask, Q, w, 2 * r + 1, hits);
   }

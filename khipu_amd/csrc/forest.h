@@ -19,7 +19,7 @@
 //      branch it passes into is OPENED, the leaf it ends at is TOUCHED
 //      (MerklePatriciaTrie.put/remove's search path);
 //   2. gather ELEMENTS: the untouched children of opened branches (unchanged subtrees:
-//      a leaf, or a branch kept as one opaque element with its cached reference), the
+//      a leaf, a branch kept as one opaque element with its cached reference, or a stub), the
 //      touched leaves no op replaced or deleted, and every upsert;
 //   3. an element build (run_build): sort, topology, and hashing of exactly the nodes
 //      on the dirty paths -- the canonical shape put / fix converge to (:183-477) -- with
@@ -98,6 +98,26 @@ KH_HD uint32_t vb_encode(const uint8_t* val, uint32_t vl, uint8_t* out) {
 }
 
 constexpr uint8_t REC_DEAD = 0, REC_LIVE = 1;
+
+// ---- a STUB: the record of a subtree the handle does not hold (a partial open from a witness:
+// MerklePatriciaTrie(rootHash, source) loads a node only when a walk enters it,
+// MerklePatriciaTrie.scala:60-66, 520-542).  A live record with db = EL_STUB (not a depth 0..64,
+// not EL_LEAF), anchored where the missing subtree hangs; it holds no key and no value:
+//   k      the key prefix above the missing node (nibbles [0, rmask)), zero past it
+//   rref   the capped reference the parent holds: always a hash (rl = 32)
+//   rbref  the hash of the node that IS missing (brl = 32): rref, unless the missing node is the
+//          branch under a present extension -- then rref is the extension's hash, rbref the branch's
+//   rmask  low byte: the depth at which the missing node starts (the anchor depth, or past the
+//          extension); STUB_BRANCH: the missing node is known to be a branch (it was met under an
+//          extension), so the stub may be re-anchored like any subtree, also once a split has cut
+//          its extension down to nothing
+// so a fill rebuilds the load's frontier item (pre = k, a = d, d = rmask, ref = rbref, pref = rref)
+// from the record alone.  With rmask > d the record still stands for the extension the store did
+// hold -- RLP[HP(nibbles d..rmask, ext), rbref], exported, proved and served by hash like the upper
+// node of a branch record -- and a key that leaves that extension does not need the branch.
+// Every reader of rdb tests for it before it reads db as a depth.
+constexpr uint8_t EL_STUB = 0xFE;
+constexpr uint16_t STUB_BRANCH = 0x100;
 
 // Node records: one 128-byte record per node (array of structures), so a probe's check
 // (trie, anchor depth, key) and a descent step read ONE 64-byte line, and a whole record
@@ -212,13 +232,18 @@ KH_HD uint64_t map_slot_of(const AMap& M, const Recs& R, uint32_t r) {
 
 // MerklePatriciaTrie.get (MerklePatriciaTrie.scala:90-147) on the records: the anchor
 // descent of a commit (a branch whose extension the key leaves, or an empty child
-// anchor, ends the search); the leaf record holding exactly `key`, or NONE
+// anchor, ends the search); the leaf record holding exactly `key`, or NONE -- or the STUB the
+// walk reaches (the key's presence is unknown: the caller tests rdb)
 KH_HD uint32_t forest_get(const AMap& M, const Recs& R, uint32_t t, const uint64_t* key) {
   uint32_t d = 0;
   for (int step = 0; step < 70; ++step) {
     const uint32_t r = map_find(M, R, t, d, key);
     if (r == NONE) return NONE;
     const uint32_t db = R.rdb[r];
+    if (db == EL_STUB) {  // (a key that leaves the present extension above a missing branch is absent)
+      const uint32_t md = R.rmask[r] & 0xFF;
+      return (md > d && lcp_nibbles(load_key(key, 0), load_key(R.key(r), 0)) < (int)md) ? NONE : r;
+    }
     if (db == EL_LEAF || db == VB_DEPTH) {  // a leaf, or a value-only branch: it holds one key
       const uint64_t* L = R.key(r);
       return (L[0] == key[0] && L[1] == key[1] && L[2] == key[2] && L[3] == key[3]) ? r : NONE;
@@ -273,9 +298,16 @@ KH_HD void elem_from_record(const Recs& R, uint32_t r, uint32_t seg, const Elems
 // element e from record r (e claimed from E.n by the caller)
 KH_HD void elem_fill(const Recs& R, uint32_t r, uint32_t seg, const Elems& E, uint64_t e) {
   if (e >= E.cap) return;  // the host sized the buffer; overflow flagged by the counter
+  // a stub is a subtree element whose "branch" is the missing node: at depth rmask with the
+  // reference rbref.  Hanging at its own anchor it has no node of its own and its cached reference
+  // (rref) is republished.  A missing branch under a present extension (rmask > d) may be
+  // re-anchored like any subtree -- the extension is re-cut over rbref, as the reference's fix
+  // merges paths without loading the branch; a stub without STUB_BRANCH is a node of unknown kind, and
+  // an anchor of it that would move is refused before anything is written (k_stub_moved).
+  const bool stub = R.rdb[r] == EL_STUB;
   for (int q = 0; q < 4; ++q) E.key[4 * e + q] = R.rk[4ull * r + q];
   E.seg[e] = seg;
-  E.db[e] = R.rdb[r];
+  E.db[e] = stub ? (uint8_t)R.rmask[r] : R.rdb[r];
   for (int q = 0; q < 4; ++q) E.bref[4 * e + q] = R.rbref[4ull * r + q];
   E.brl[e] = R.rbrl[r];
   E.vo[e] = R.rvo[r];

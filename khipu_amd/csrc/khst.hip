@@ -3292,7 +3292,8 @@ static void copy_root(const BuildOut& O, uint64_t r, uint8_t* out32) {
 __global__ void __launch_bounds__(BS) k_f_descend(FOps O, AMap M, Recs R, uint32_t* touched, uint8_t* replaced,
                                                   uint32_t* tlist, unsigned long long* ctr, uint8_t* vbf) {
   const uint64_t o = (uint64_t)blockIdx.x * BS + threadIdx.x;
-  // ctr[0] touched list size, [1] replaced leaves, [2] error, [3] refusal, [6] value-only
+  // ctr[0] touched list size, [1] replaced leaves, [2] error, [3] refusal (bit 0: a delete of a
+  // value-only branch's key, bit 1: an op reached a stub, forest.h EL_STUB), [6] value-only
   // branches made (vbf[o]: op o puts a value-only branch, forest.h VB_DEPTH).  Every op of a commit passes
   // through its trie's top records: the touched flag is read before it is exchanged, so
   // only the first few ops contend for a hot record's atomic (a stale 0 from the vector
@@ -3349,8 +3350,17 @@ __global__ void __launch_bounds__(BS) k_f_descend(FOps O, AMap M, Recs R, uint32
             r = NONE;  // (cannot happen: another key leaves the extension above it)
           }
           active = lost = false;
-        } else if (lcp_nibbles(load_key(K, 0), load_key(R.key(r), 0)) < (int)db) {
-          r = NONE;  // diverges in the extension
+        } else if (const int lcp = lcp_nibbles(load_key(K, 0), load_key(R.key(r), 0)); lcp < (int)db) {
+          // diverges in the extension -- or a stub (EL_STUB is past every depth, so the walk that
+          // passes through a branch pays nothing for it).  A key that leaves the present
+          // extension above a missing branch does not need the branch: the stub is gathered and
+          // re-cut like any subtree (forest.h elem_fill); otherwise the subtree is not held: a
+          // missing node, marked and listed
+          const uint32_t md = R.rmask[r] & 0xFF;
+          if (db == EL_STUB && !(md > d && lcp < (int)md))
+            atomicOr(&ctr[3], 2ULL);
+          else
+            r = NONE;
           active = lost = false;
         } else {
           d = db + 1;
@@ -3523,6 +3533,8 @@ __global__ void __launch_bounds__(GATHER_BS) k_f_gather(AMap M, Recs R, const ui
         if (db == EL_LEAF) {
           want = v == 0 && !replaced[r];
           er = r;
+        } else if (db == EL_STUB) {
+          // a stub the descent reached: the commit is refused at the sync below (nothing to gather)
         } else if ((R.rmask[r] >> v) & 1) {
           uint64_t ck[4] = {R.rk[4ull * r], R.rk[4ull * r + 1], R.rk[4ull * r + 2], R.rk[4ull * r + 3]};
           set_nibble(ck, db, v);
@@ -3636,7 +3648,10 @@ __global__ void __launch_bounds__(BS) k_f_elem_recs(Topo T, Elems E, const uint3
   }
   v.t = tries[T.sseg ? T.sseg[i] : 0];
   v.d = (uint8_t)(T.lf_pd[i] + 1);
-  v.db = T.el_db[i];
+  // (a re-anchored stub -- a missing branch whose extension was re-cut -- stays a stub: its
+  // element stood for it with db = the branch depth, forest.h elem_fill)
+  // (only a moved subtree element reads its source's db: leaves and upserts, most of what is written here, do not)
+  v.db = (src != NONE && T.el_db[i] != EL_LEAF && R.rdb[r] == EL_STUB) ? EL_STUB : T.el_db[i];
   v.mask = src == NONE ? 0 : R.rmask[r];  // a re-anchored subtree keeps its children
   v.live = REC_LIVE;
   const uint32_t L = T.lf_rlen[i];
@@ -3807,7 +3822,7 @@ struct JSeg {  // one journaled commit: its saved records and map-slot log range
   uint64_t ipos = 0, in = 0;  // ... and the inserts, 3 words per entry (slot, old tag, old record)
 };
 struct Savepoint {
-  uint64_t rn = 0, heap_n = 0, nleaves = 0, mused = 0, rdead = 0, map_epoch = 0;
+  uint64_t rn = 0, heap_n = 0, nleaves = 0, mused = 0, rdead = 0, map_epoch = 0, nstubs = 0;
   uint8_t root[32] = {};
   std::vector<uint32_t> tries;  // the last commit's touched tries and roots (kh_forest_last_roots)
   std::vector<uint8_t> roots;
@@ -3846,6 +3861,11 @@ struct kh_trie {
   DevBuf heap;
   uint64_t heap_n = 0;
   uint64_t nleaves = 0;
+  // a partial handle (forest.h EL_STUB): its live stubs, and the (trie id, hash to fetch) pairs of
+  // the last commit if it was refused with KH_ENODE (kh_trie_missing)
+  uint64_t nstubs = 0;
+  std::vector<uint32_t> miss_tries;
+  std::vector<uint8_t> miss_hashes;
   uint8_t root[32] = {};
   DevBuf ws, elout, eloutb, em;  // commit scratch, element-build outputs, last write-back set
   DevBuf tlb, ebuf, tbuf, ubuf, selb, merr;  // touched list, elements, trie ids + roots, upsert offsets, selections
@@ -4140,6 +4160,23 @@ __global__ void __launch_bounds__(BS) k_open_level(OItems I, uint64_t ni, OItems
   }
 }
 
+// the (trie id, hash) pairs a refusal kernel listed (k_stub_missing / k_stub_moved) into the
+// handle's missing list: one sync
+static void stub_missing_read(kh_trie* h, const uint32_t* d_trie, const uint64_t* d_hash,
+                              const unsigned long long* d_cnt, uint64_t cap) {
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  HIPCHK(hipMemcpyAsync(c->h_pinned + 9, d_cnt, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t k = std::min<uint64_t>(c->h_pinned[9], cap);
+  h->miss_tries.resize(k);
+  h->miss_hashes.resize(k * 32);
+  if (!k) return;
+  HIPCHK(hipMemcpyAsync(h->miss_tries.data(), d_trie, k * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h->miss_hashes.data(), d_hash, k * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+}
+
 struct FCommit {  // one commit's inputs (device buffers)
   const uint32_t* up_trie = nullptr;  // nullable: trie 0
   const uint8_t* up_keys = nullptr;
@@ -4208,9 +4245,22 @@ static JSeg journal_reserve(kh_trie* h, uint64_t nrec, uint64_t nmap) {
 // key winning; deleting an absent key is a no-op.  Fills h->tries / h->roots.  A refused
 // batch (KH_EINVAL) leaves the handle as it was, its last roots and write-back set included;
 // with a savepoint open (h->sps) every change is journaled for kh_trie_rollback.
+static void stub_missing_read(kh_trie* h, const uint32_t* d_trie, const uint64_t* d_hash,
+                              const unsigned long long* d_cnt, uint64_t cap);
+__global__ void k_stub_missing(Recs R, const uint32_t* list, uint64_t n, uint64_t cap, uint32_t* out_trie,
+                               uint64_t* out_hash, unsigned long long* cnt);
+__global__ void k_stub_moved(Recs R, const uint32_t* sidx, const int8_t* pd, const uint32_t* src, const uint8_t* oldd,
+                             uint64_t m, uint64_t cap, uint32_t* out_trie, uint64_t* out_hash,
+                             unsigned long long* cnt);
+static const char* const MSG_STUB =
+    "the commit needs a node the handle does not hold (MPTNodeMissingException): kh_trie_missing lists the hashes, "
+    "kh_trie_fill_nodes takes the nodes; the trie is unchanged";
+
 static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   kh_ctx* c = h->c;
   hipStream_t st = c->st;
+  h->miss_tries.clear();
+  h->miss_hashes.clear();
   if (F.inputs_ready) HIPCHK(hipStreamWaitEvent(st, F.inputs_ready, 0));
   if (stats) memset(stats, 0, sizeof(*stats));
   const bool journal = !h->sps.empty();
@@ -4405,6 +4455,22 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   const uint64_t ntl = c->h_pinned[0], nrep = c->h_pinned[1];
   if (c->h_pinned[2] == 3) throw KhError{KH_EINTERNAL, "forest descent: corrupt anchor map"};
   if (c->h_pinned[3]) {  // nothing has changed yet: clear the descent's flags and refuse the batch
+    const bool stub = (c->h_pinned[3] & 2) != 0;
+    if (stub) {  // every stub an op reached is in the touched list, once: the hashes to fetch
+      Layout Lm;
+      uint32_t* mt;
+      uint64_t* mh;
+      unsigned long long* mc;
+      Lm.add(mt, ntl);
+      Lm.add(mh, ntl * 4);
+      Lm.add(mc, 8);
+      place(h->selb, Lm);
+      HIPCHK(hipMemsetAsync(mc, 0, 8, st));
+      hipLaunchKernelGGL(k_stub_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)tlist, ntl, ntl,
+                         mt, mh, mc);
+      LAUNCH_CHECK();
+      stub_missing_read(h, mt, mh, mc, ntl);
+    }
     if (ntl) {
       hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
                          (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p);
@@ -4412,6 +4478,7 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       HIPCHK(hipStreamSynchronize(st));
     }
     h->flags_dirty = false;
+    if (stub) throw KhError{KH_ENODE, MSG_STUB};
     throw KhError{KH_EINVAL,
                   "remove of a key held by a value-only branch: khipu's fix of the emptied branch throws "
                   "MPTException(\"Branch with no subvalues\") (MerklePatriciaTrie.scala:323-370,430-477); the trie "
@@ -4488,6 +4555,36 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     B = c->last_B;
     m = c->T.m;
     if (m != ne) throw KhError{KH_EINTERNAL, "forest: duplicate elements"};
+    // a handle that holds stubs: one whose anchor would move (a delete left it its parent's only
+    // child) is a missing node too, seen only now that the topology is known.  One more sync,
+    // before any record or map write; a handle without stubs never comes here.
+    if (h->nstubs) {
+      Layout Lm;
+      uint32_t* mt;
+      uint64_t* mh;
+      unsigned long long* mc;
+      const uint64_t mcap = std::min<uint64_t>(m, h->nstubs);
+      Lm.add(mt, mcap);
+      Lm.add(mh, mcap * 4);
+      Lm.add(mc, 8);
+      place(h->selb, Lm);
+      HIPCHK(hipMemsetAsync(mc, 0, 8, st));
+      hipLaunchKernelGGL(k_stub_moved, GRID(m, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)c->T.sidx,
+                         (const int8_t*)c->T.lf_pd, (const uint32_t*)E.src, (const uint8_t*)E.oldd, m, mcap, mt, mh, mc);
+      LAUNCH_CHECK();
+      stub_missing_read(h, mt, mh, mc, mcap);
+      if (!h->miss_tries.empty()) {  // nothing has changed yet: as the descent's refusal above
+        if (ntl) {
+          hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
+                             (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p);
+          LAUNCH_CHECK();
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        h->flags_dirty = false;
+        h->heap_n = hb;  // (the upserts' values past it are dropped)
+        throw KhError{KH_ENODE, MSG_STUB};
+      }
+    }
   }
   // Without a write-back set or a map rebuild, the commit returns as soon as its roots are on
   // the host; the records and the anchor map follow on the stream (the next call is ordered
@@ -4670,6 +4767,7 @@ static void trie_savepoint(kh_trie* h) {
   sp->rn = h->rn;
   sp->heap_n = h->heap_n;
   sp->nleaves = h->nleaves;
+  sp->nstubs = h->nstubs;
   sp->mused = h->mused;
   sp->rdead = h->rdead;
   sp->map_epoch = h->map_epoch;
@@ -4719,6 +4817,7 @@ static void trie_rollback(kh_trie* h) {
   h->rn = sp.rn;
   h->heap_n = sp.heap_n;
   h->nleaves = sp.nleaves;
+  h->nstubs = sp.nstubs;
   h->mused = sp.mused;
   h->rdead = sp.rdead;
   memcpy(h->root, sp.root, 32);
@@ -4827,6 +4926,7 @@ static kh_trie* trie_copy(kh_trie* h) {
   if (h->heap_n) HIPCHK(hipMemcpyAsync(n->heap.p, h->heap.p, h->heap_n, hipMemcpyDeviceToDevice, st));
   n->heap_n = h->heap_n;
   n->nleaves = h->nleaves;
+  n->nstubs = h->nstubs;
   memcpy(n->root, h->root, 32);
   n->tries = h->tries;
   n->roots = h->roots;
@@ -6224,6 +6324,10 @@ int kh_block_commit(kh_trie* state, kh_trie* storage, const uint32_t* d_s_up_tri
   if (!state || state->forest || !storage || !storage->forest) return set_err(KH_EINVAL, "need a state trie and a forest");
   if (state->home->dev != storage->home->dev) return set_err(KH_EINVAL, "state trie and forest on different devices");
   PairLock pl(state->lk, storage->lk);
+  for (kh_trie* x : {state, storage}) {  // (each handle's missing list is this call's)
+    x->miss_tries.clear();
+    x->miss_hashes.clear();
+  }
   API_TRY({
     kh_ctx* c = state->c;
     HIPCHK(hipSetDevice(c->dev));
@@ -6443,7 +6547,7 @@ __global__ void __launch_bounds__(BS) k_get_copy(Recs R, const uint8_t* heap, co
   const uint64_t o = (uint64_t)blockIdx.x * BS + threadIdx.x;
   if (o >= n) return;
   const uint32_t r = rec[o];
-  found[o] = r != NONE;
+  found[o] = r == NONE ? 0 : R.rdb[r] == EL_STUB ? 2 : 1;  // (2: KH_FOUND_UNKNOWN, the walk reached a stub)
   if (r == NONE) return;
   const uint8_t* src = heap + R.rvo[r];
   uint8_t* dst = out + voff[o];
@@ -6993,9 +7097,15 @@ static int verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t*
 __global__ void k_load_root_flags(const uint64_t* roots, uint64_t k, uint32_t* flag);
 __global__ void k_load_roots(const uint64_t* roots, uint64_t k, const uint32_t* flag, const uint32_t* pos, LItems N);
 __global__ void k_load_resident(AMap M, Recs R, const uint32_t* tries, uint64_t k, unsigned long long* n_resident);
-__global__ void k_load_count(LItems I, uint64_t ni, NStore S, LCounts C, unsigned long long* tot);
+__global__ void k_load_count(LItems I, uint64_t ni, NStore S, LCounts C, unsigned long long* tot, int partial);
 __global__ void k_load_fill(LItems I, uint64_t ni, NStore S, LCounts C, LItems N, const uint32_t* tries, uint8_t* recs,
-                            uint64_t rbase, uint64_t rcap, uint8_t* heap, uint64_t hbase, uint64_t heap_cap);
+                            uint64_t rbase, uint64_t rcap, uint8_t* heap, uint64_t hbase, uint64_t heap_cap,
+                            int partial);
+__global__ void k_fill_flags(Recs R, uint64_t n, NStore S, uint32_t* flag);
+__global__ void k_fill_items(Recs R, uint64_t n, const uint32_t* flag, const uint32_t* pos, LItems N, uint32_t* tries,
+                             uint32_t* list);
+__global__ void k_need(AMap M, Recs R, const uint64_t* K, const uint32_t* trie, uint64_t n, uint8_t* flag,
+                       uint64_t* hash);
 __global__ void k_load_missing(LItems I, uint64_t ni, const uint32_t* miss, const uint32_t* mpos, uint64_t cap,
                                uint32_t* out_idx, uint64_t* out_hash);
 __global__ void k_roots_flags(Recs R, uint64_t n, uint32_t* flag);
@@ -7024,25 +7134,38 @@ static LItems litems_carve(DevBuf& b, uint64_t cap) {
 // (device buffers) into forest h, beside what it holds.  All or nothing: a refusal or failure
 // before the anchor map is touched leaves no record past the old count (the slots cleared) and
 // every host-side field as it was.  With a savepoint open the map inserts are journaled.
+//
+// mode LOAD_PARTIAL (kh_forest_load_partial, kh_trie_open_partial): a hash absent from the store
+// below a root makes a stub (forest.h EL_STUB) instead of ending the round; a missing root is
+// reported as ever.  mode LOAD_FILL (kh_trie_fill_nodes; tries, roots32, k unused): round 0 is the
+// live stubs whose missing node the store holds, in record order; the rounds append as a partial
+// load does, and only after the last one do the listed stubs leave the map and die, the new
+// records taking their anchors -- so a failure before that leaves the handle as it was.
+enum LoadMode { LOAD_FULL = 0, LOAD_PARTIAL = 1, LOAD_FILL = 2 };
 static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
                         const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
-                        uint64_t* n_missing, kh_stats* stats) {
+                        uint64_t* n_missing, kh_stats* stats, LoadMode mode = LOAD_FULL,
+                        uint64_t* n_decoded = nullptr) {
   kh_ctx* c = h->c;
   hipStream_t st = c->st;
   if (stats) memset(stats, 0, sizeof(*stats));
+  const bool fill = mode == LOAD_FILL;
+  if (fill) k = 0;
   if (k >= (1ULL << 31) || n >= (1ULL << 31)) throw KhError{KH_EINVAL, "trie list or node store too large"};
-  {
+  if (fill && !h->sps.empty()) throw KhError{KH_EINVAL, "kh_trie_fill_nodes: a savepoint is open"};
+  if (!fill) {
     std::vector<uint32_t> ids(tries, tries + k);
     std::sort(ids.begin(), ids.end());
     if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
       throw KhError{KH_EINVAL, "kh_forest_load_nodes: a trie id is listed twice"};
   }
   trie_settle(h);
-  if (k == 0) {
+  if (fill ? (h->nstubs == 0 || n == 0 || h->rn == 0) : k == 0) {
     ++h->epoch;
     return;
   }
   HIPCHK(hipEventRecord(c->ev[6], st));
+  const uint64_t nscan = fill ? h->rn : 0;  // fill: the records scanned for stubs
   // the list on the device, the roots to walk (not the empty trie's) and the resident check
   Layout Lr;
   uint32_t *dtries, *rflag, *rpos, *dmidx;
@@ -7050,17 +7173,25 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
   unsigned long long* tot;
   char* rscr;
   const uint64_t mcap = std::min<uint64_t>(miss_cap, 1ULL << 24);
-  Lr.add(dtries, k);
+  const uint64_t kk = fill ? nscan : k;  // (fill: a list entry per stub found, at most one per record)
+  uint32_t* slist = nullptr;            // fill: the stubs of round 0
+  Lr.add(dtries, kk);
   Lr.add(droots, k * 4);
-  Lr.add_all(k, rflag, rpos);
-  Lr.add(rscr, scan_scratch_bytes(k + 1, 4));
+  Lr.add_all(kk, rflag, rpos);
+  Lr.add(rscr, scan_scratch_bytes(kk + 1, 4));
   Lr.add(tot, 8);
   Lr.add(dmidx, mcap + 1);
   Lr.add(dmhash, (mcap + 1) * 4);
+  Lr.add(slist, nscan);
   place(h->gbuf, Lr);
-  HIPCHK(hipMemcpyAsync(dtries, tries, k * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(droots, roots32, k * 32, hipMemcpyHostToDevice, st));
+  if (!fill) {
+    HIPCHK(hipMemcpyAsync(dtries, tries, k * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(droots, roots32, k * 32, hipMemcpyHostToDevice, st));
+  }
   HIPCHK(hipMemsetAsync(tot, 0, 64, st));
+  uint64_t ni = 0;
+  uint32_t max_id = 0;
+  if (!fill) {
   if (h->rn && h->mcap) {
     hipLaunchKernelGGL(k_load_resident, GRID(k, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint32_t*)dtries, k,
                        tot + 6);
@@ -7072,12 +7203,12 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
   HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (c->h_pinned[6]) throw KhError{KH_EINVAL, "kh_forest_load_nodes: a listed trie is already resident"};
-  uint64_t ni = (uint32_t)c->h_pinned[0];
-  uint32_t max_id = 0;
+  ni = (uint32_t)c->h_pinned[0];
   for (uint64_t j = 0; j < k; ++j) max_id = std::max(max_id, tries[j]);
   if (ni == 0) {  // every root is the empty trie's
     ++h->epoch;
     return;
+  }
   }
   // the store, keyed by kec256 of each encoding (content addressed)
   Layout L;
@@ -7100,16 +7231,37 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
   }
   HIPCHK(hipEventRecord(c->ev[0], st));  // (stats: the store is hashed and sorted)
   const uint64_t rn0 = h->rn;
-  uint64_t heap_cur = h->heap_n, keys = 0;
+  uint64_t heap_cur = h->heap_n, keys = 0, stubs_made = 0, decoded = 0, nfilled = 0;
   uint32_t rounds = 0;
   bool map_stage = false;
   try {
     DevBuf fa, fb, cb;
-    LItems cur = litems_carve(fa, ni);
-    hipLaunchKernelGGL(k_load_roots, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, (const uint32_t*)rflag,
-                       (const uint32_t*)rpos, cur);
-    LAUNCH_CHECK();
+    LItems cur{};
+    if (fill) {  // round 0: the stubs the store resolves, in record order
+      hipLaunchKernelGGL(k_fill_flags, GRID(nscan, BS), dim3(BS), 0, st, recs_of(h), nscan, NS, rflag);
+      LAUNCH_CHECK();
+      scan_exclusive<uint32_t>(rflag, rpos, nscan, (uint32_t*)tot, rscr, st);
+      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      ni = nfilled = (uint32_t)c->h_pinned[0];
+      if (ni == 0) {  // no stub names a node of the store: nothing to do
+        ++h->epoch;
+        if (n_decoded) *n_decoded = 0;
+        return;
+      }
+      cur = litems_carve(fa, ni);
+      hipLaunchKernelGGL(k_fill_items, GRID(nscan, BS), dim3(BS), 0, st, recs_of(h), nscan, (const uint32_t*)rflag,
+                         (const uint32_t*)rpos, cur, dtries, slist);
+      LAUNCH_CHECK();
+    } else {
+      cur = litems_carve(fa, ni);
+      hipLaunchKernelGGL(k_load_roots, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k,
+                         (const uint32_t*)rflag, (const uint32_t*)rpos, cur);
+      LAUNCH_CHECK();
+    }
     for (; ni && rounds < 80; ++rounds) {
+      // (a root is never a stub: round 0 of a partial load reports a missing root as the full load does)
+      const int partial = fill || (mode == LOAD_PARTIAL && rounds > 0);
       // count, scans, one sync
       Layout Lc;
       LCounts C{};
@@ -7121,7 +7273,7 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
       Lc.add(scr, scan_scratch_bytes(ni + 1, 8));
       place(cb, Lc);
       HIPCHK(hipMemsetAsync(tot, 0, 64, st));
-      hipLaunchKernelGGL(k_load_count, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, tot);
+      hipLaunchKernelGGL(k_load_count, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, tot, partial);
       LAUNCH_CHECK();
       scan_exclusive<uint32_t>(C.child, C.child, ni, (uint32_t*)tot, scr, st);
       scan_exclusive<uint32_t>(C.rec, C.rec, ni, (uint32_t*)(tot + 1), scr, st);
@@ -7131,6 +7283,8 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
       const uint64_t nchild = (uint32_t)c->h_pinned[0], nrec = (uint32_t)c->h_pinned[1], nval = c->h_pinned[2];
       const uint64_t code = c->h_pinned[3], nmiss = c->h_pinned[4];
       keys += c->h_pinned[5];
+      stubs_made += c->h_pinned[6];
+      decoded += c->h_pinned[7];
       if (code == OPEN_VALUE) throw KhError{KH_EINVAL, "a branch with a value: not a secure trie"};
       if (code) throw KhError{KH_EINVAL, "the store holds a node that is not a canonical secure-trie node"};
       if (nmiss) {  // every missing reference of this round (MPTNodeMissingException), then stop
@@ -7154,7 +7308,8 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
       if (hneed > h->heap.cap) regrow(h->heap, heap_cur, hneed + hneed / 4, st);
       LItems nxt = litems_carve(rounds & 1 ? fa : fb, std::max<uint64_t>(nchild, 1));
       hipLaunchKernelGGL(k_load_fill, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, nxt, (const uint32_t*)dtries,
-                         (uint8_t*)h->recs.p, h->rn, h->rcap, (uint8_t*)h->heap.p, heap_cur, (uint64_t)h->heap.cap);
+                         (uint8_t*)h->recs.p, h->rn, h->rcap, (uint8_t*)h->heap.p, heap_cur, (uint64_t)h->heap.cap,
+                         partial);
       LAUNCH_CHECK();
       h->rn += nrec;  // (a later regrow keeps the records of the earlier rounds)
       heap_cur += nval;
@@ -7166,6 +7321,13 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
     const uint64_t nnew = h->rn - rn0;
     HIPCHK(hipEventRecord(c->ev[1], st));  // (stats: the rounds are done)
     map_stage = true;
+    if (fill) {  // the resolved stubs leave the map and die; the new records take their anchors below
+      hipLaunchKernelGGL(k_map_delete, GRID(nfilled, BS), dim3(BS), 0, st, map_of(h), recs_of(h),
+                         (const uint32_t*)slist, nfilled, (const uint32_t*)nullptr, (uint64_t)0,
+                         (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p, (uint64_t*)nullptr);
+      LAUNCH_CHECK();
+      h->rdead += nfilled;
+    }
     if (h->mcap == 0 || 2 * (h->mused + nnew + 1024) > h->mcap) {
       map_rebuild(h, 1024);  // (syncs; with a savepoint open its map_epoch bump is the journal entry)
     } else if (nnew) {
@@ -7204,7 +7366,9 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
   }
   h->heap_n = heap_cur;
   h->nleaves += keys;
-  h->tid_bits = std::max(h->tid_bits, std::min(bits_for((uint64_t)max_id + 1) + 2, 32u));
+  h->nstubs = h->nstubs + stubs_made - nfilled;
+  if (n_decoded) *n_decoded = decoded;
+  if (!fill) h->tid_bits = std::max(h->tid_bits, std::min(bits_for((uint64_t)max_id + 1) + 2, 32u));
   ++h->epoch;
   HIPCHK(hipEventRecord(c->ev[7], st));
   HIPCHK(hipEventSynchronize(c->ev[7]));
@@ -7301,6 +7465,7 @@ static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t
   HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));  // (ids is a host temporary)
   const uint64_t nl = (uint32_t)c->h_pinned[0], nkeys = c->h_pinned[1], ntries = c->h_pinned[2];
+  const uint64_t nstub = c->h_pinned[3];
   if (nl == 0) return;
   ++h->epoch;
   hipLaunchKernelGGL(k_evict_list, GRID(n, BS), dim3(BS), 0, st, n, (const uint32_t*)flag, (const uint32_t*)pos, nl,
@@ -7313,6 +7478,7 @@ static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t
   HIPCHK(hipStreamSynchronize(st));
   h->rdead += nl;
   h->nleaves -= nkeys;
+  h->nstubs -= nstub;
   *n_evicted = ntries;
 }
 
@@ -7446,6 +7612,210 @@ int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8
       return KH_OK;
     }
     return trie_by_hash(h, hashes32, n, found, rlp, rlp_cap, off, rlp_len);
+  })
+}
+
+// ---- partial handles: open / load from a witness, fill, and what a refused commit needs
+// a host node store into the context's staging buffers (in_vals, in_voff); checks as the host loads
+static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint64_t n) {
+  if (n && !off) return set_err(KH_EINVAL, "null buffer");
+  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
+  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
+  const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
+  c->in_vals.ensure(bytes + 64);
+  c->in_voff.ensure((n + 1) * 8 + 64);
+  std::vector<uint64_t> rel(n + 1, 0);
+  for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
+  if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return KH_OK;
+}
+
+int kh_trie_open_partial(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                         uint32_t flags, uint8_t missing32[32], kh_trie** out) {
+  if (!out || !root32) return set_err(KH_EINVAL, "null root or handle");
+  if (n && (!d_enc || !d_off)) return set_err(KH_EINVAL, "null buffer");
+  const bool host = !c;  // (as kh_forest_open: the context the *_host entry points use, a private handle)
+  kh_trie* h = nullptr;
+  API_TRY({
+    if (!c) c = shared_ctx(current_device());
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    h = trie_new(c, flags, false);
+    try {  // the forest load with the one trie id 0 (a missing root: KH_ENODE, its hash in missing32)
+      const uint32_t id = 0;
+      uint32_t midx = 0;
+      uint8_t m32[32];
+      uint64_t nm = 0;
+      try {
+        forest_load(h, &id, root32, 1, d_enc, d_off, n, &midx, m32, 1, &nm, nullptr, LOAD_PARTIAL);
+      } catch (...) {
+        if (nm && missing32) memcpy(missing32, m32, 32);
+        throw;
+      }
+      memcpy(h->root, root32, 32);
+      if (host) make_private(h);
+    } catch (...) {
+      delete h;
+      h = nullptr;
+      throw;
+    }
+    *out = h;
+  })
+}
+
+int kh_trie_open_partial_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
+                              uint32_t flags, uint8_t missing32[32], kh_trie** out) {
+  if (!out || !root32 || (n && (!enc || !off))) return set_err(KH_EINVAL, "null input");
+  API_TRY({
+    kh_ctx* c = shared_ctx(current_device());
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    int rc = stage_store(c, enc, off, n);
+    if (rc != KH_OK) return rc;
+    rc = kh_trie_open_partial(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags,
+                              missing32, out);
+    if (rc != KH_OK) return rc;
+    try {
+      make_private(*out);
+    } catch (...) {
+      delete *out;
+      *out = nullptr;
+      throw;
+    }
+  })
+}
+
+int kh_forest_load_partial(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
+                           const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
+                           uint64_t* n_missing, kh_stats* stats) {
+  if (n_missing) *n_missing = 0;
+  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
+  if ((k && (!tries || !roots32)) || (n && (!d_enc || !d_off)) || (miss_cap && (!miss_idx || !miss32)))
+    return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(f);
+    HIPCHK(hipSetDevice(f->c->dev));
+    forest_load(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL);
+  })
+}
+
+int kh_forest_load_partial_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
+                                const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx,
+                                uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
+  if (n_missing) *n_missing = 0;
+  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
+  if ((k && (!tries || !roots32)) || (miss_cap && (!miss_idx || !miss32))) return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(f);
+    kh_ctx* c = f->c;
+    HIPCHK(hipSetDevice(c->dev));
+    const int rc = stage_store(c, enc, off, n);
+    if (rc != KH_OK) return rc;
+    forest_load(f, tries, roots32, k, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, miss_idx, miss32,
+                miss_cap, n_missing, stats, LOAD_PARTIAL);
+  })
+}
+
+int kh_trie_fill_nodes(kh_trie* h, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n, uint64_t* n_decoded,
+                       kh_stats* stats) {
+  if (n_decoded) *n_decoded = 0;
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  if (n && (!d_enc || !d_off)) return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(h);
+    HIPCHK(hipSetDevice(h->c->dev));
+    forest_load(h, nullptr, nullptr, 0, d_enc, d_off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded);
+  })
+}
+
+int kh_trie_fill_nodes_host(kh_trie* h, const uint8_t* enc, const uint64_t* off, uint64_t n, uint64_t* n_decoded,
+                            kh_stats* stats) {
+  if (n_decoded) *n_decoded = 0;
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    const int rc = stage_store(c, enc, off, n);
+    if (rc != KH_OK) return rc;
+    forest_load(h, nullptr, nullptr, 0, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, nullptr,
+                nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded);
+  })
+}
+
+int kh_trie_stubs(const kh_trie* h, uint64_t* n) {
+  if (!h || !n) return set_err(KH_EINVAL, "null handle");
+  HANDLE_LOCK(h);
+  *n = h->nstubs;
+  return KH_OK;
+}
+
+int kh_trie_missing(const kh_trie* h, uint32_t* tries, uint8_t* hashes32, uint64_t cap, uint64_t* n) {
+  if (!h || !n) return set_err(KH_EINVAL, "null handle or count");
+  HANDLE_LOCK(h);
+  const uint64_t k = h->miss_tries.size();
+  *n = k;
+  if (k && cap == 0) return KH_ENOSPC;  // the size query: kh_last_error keeps the refused commit's message
+  if (k > cap || (k && (!tries || !hashes32))) return set_err(KH_ENOSPC, "missing-node output too small");
+  if (k) {
+    memcpy(tries, h->miss_tries.data(), k * 4);
+    memcpy(hashes32, h->miss_hashes.data(), k * 32);
+  }
+  return KH_OK;
+}
+
+int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
+                      uint8_t* need_flag, uint8_t* need32) {
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  if (n && (!keys || !need_flag || !need32)) return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
+    if (!(h->flags & KH_HASH_KEYS) && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
+    if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
+    if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
+    if (n == 0) return KH_OK;
+    trie_settle(h);
+    if (!(h->nstubs && h->rn && h->mcap)) {  // no stub to reach
+      memset(need_flag, 0, n);
+      memset(need32, 0, n * 32);
+      return KH_OK;
+    }
+    Layout Lk, L;
+    uint8_t *dk, *df;
+    uint32_t* dt;
+    uint64_t *K, *dh;
+    Lk.add(dk, n * klen + 64);
+    Lk.add(dt, n, trie != nullptr);
+    place(c->in_keys, Lk);
+    L.add(K, n * 4 + 8);
+    L.add(dh, n * 4);
+    L.add(df, n + 64);
+    place(h->gbuf, L);
+    HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
+    if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, st));
+    if (h->flags & KH_HASH_KEYS) {
+      if (klen <= 135)
+        hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
+      else
+        hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
+      LAUNCH_CHECK();
+    } else {
+      HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
+    }
+    hipLaunchKernelGGL(k_need, GRID(n, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint64_t*)K,
+                       (const uint32_t*)dt, n, df, dh);
+    LAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(need_flag, df, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(need32, dh, n * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
   })
 }
 

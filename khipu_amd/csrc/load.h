@@ -236,9 +236,46 @@ KH_HD bool load_locate(const LItems& I, uint64_t i, const NStore& S, uint32_t* p
   return true;
 }
 
-// count pass, item i; returns the OPEN_* code (OPEN_MISSING: C.miss[i] is set)
+// the stub (forest.h EL_STUB) a partial load leaves for frontier item i, whose hash is absent from
+// the store: the item itself, kept as a record (load_stub_item is the way back)
+KH_HD void load_stub_record(const LItems& I, uint64_t i, uint32_t trie, uint8_t* recs, uint64_t r, uint64_t rcap) {
+  if (r >= rcap) return;
+  RecVal v;
+  for (int q = 0; q < 4; ++q) {
+    v.k[q] = I.pre[4 * i + q];
+    v.ref[q] = I.pref[4 * i + q];
+    v.bref[q] = I.ref[4 * i + q];
+  }
+  v.t = trie;
+  v.d = I.a[i];
+  v.db = EL_STUB;
+  v.mask = (uint16_t)(I.d[i] | (I.d[i] > I.a[i] ? STUB_BRANCH : 0));  // (an extension's child is a branch)
+  v.live = REC_LIVE;
+  v.rl = I.prl[i];
+  v.brl = 32;
+  v.vl = 0;
+  v.vo = 0;
+  rec_store(recs, r, v);
+}
+// fill: frontier item t of list index j from stub record r
+KH_HD void load_stub_item(const Recs& R, uint64_t r, const LItems& N, uint64_t t, uint32_t j) {
+  if (t >= N.cap) return;
+  for (int q = 0; q < 4; ++q) {
+    N.pre[4 * t + q] = R.rk[4 * r + q];
+    N.ref[4 * t + q] = R.rbref[4 * r + q];
+    N.pref[4 * t + q] = R.rref[4 * r + q];
+  }
+  N.a[t] = R.rd[r];
+  N.d[t] = (uint8_t)R.rmask[r];
+  N.rl[t] = 32;
+  N.prl[t] = R.rrl[r];
+  N.j[t] = j;
+}
+
+// count pass, item i; returns the OPEN_* code (OPEN_MISSING: C.miss[i] is set).  partial: a hash
+// absent from the store makes a stub (one record) instead
 KH_HD unsigned long long load_count_item(const LItems& I, uint64_t i, const NStore& S, const LCounts& C,
-                                         uint32_t* is_key) {
+                                         uint32_t* is_key, bool partial = false) {
   C.child[i] = 0;
   C.rec[i] = 0;
   C.val[i] = 0;
@@ -248,6 +285,10 @@ KH_HD unsigned long long load_count_item(const LItems& I, uint64_t i, const NSto
   uint32_t pos = NONE, L;
   const uint8_t* e;
   if (!load_locate(I, i, S, &pos, &e, &L)) {
+    if (partial) {  // the subtree stays a stub: one record, no children, no value
+      C.rec[i] = 1;
+      return OPEN_OK;
+    }
     C.miss[i] = 1;
     return OPEN_MISSING;
   }
@@ -265,10 +306,13 @@ KH_HD unsigned long long load_count_item(const LItems& I, uint64_t i, const NSto
 // fill pass, item i: C holds the exclusive scans of the counts (src as the count pass left it)
 KH_HD void load_fill_item(const LItems& I, uint64_t i, const NStore& S, const LCounts& C, const LItems& N,
                           const uint32_t* tries, uint8_t* recs, uint64_t rbase, uint64_t rcap, uint8_t* heap,
-                          uint64_t hbase, uint64_t heap_cap) {
+                          uint64_t hbase, uint64_t heap_cap, bool partial = false) {
   uint32_t pos = C.src[i], L;
   const uint8_t* e;
-  if (I.rl[i] == 32 && pos == NONE) return;
+  if (I.rl[i] == 32 && pos == NONE) {  // absent from the store: nothing, or the stub the count pass counted
+    if (partial) load_stub_record(I, i, tries[I.j[i]], recs, rbase + C.rec[i], rcap);
+    return;
+  }
   if (!load_locate(I, i, S, &pos, &e, &L)) return;
   LoadFill sink{N, C.child[i], I.j[i], recs, rbase + C.rec[i], rcap, tries[I.j[i]], heap, hbase + C.val[i], heap_cap};
   load_node(e, L, I.rl[i] == 32, I.ref + 4 * i, I.pre + 4 * i, I.a[i], I.d[i], I.pref + 4 * i, I.prl[i], sink);
@@ -284,5 +328,6 @@ KH_HD bool load_in_list(const Recs& R, uint64_t r, const uint32_t* tries, uint32
   return s < nt && tries[s] == t;
 }
 KH_HD bool load_holds_key(const Recs& R, uint64_t r) { return R.rdb[r] == EL_LEAF || R.rdb[r] == VB_DEPTH; }
+KH_HD bool load_is_stub(const Recs& R, uint64_t r) { return R.rlive[r] == REC_LIVE && R.rdb[r] == EL_STUB; }
 
 }  // namespace khst

@@ -16,13 +16,20 @@ namespace khst {
 
 // The proof walk of one key: hit(h) for every listed node in root-first order; returns whether
 // the key is present.  The count pass and the fill pass both run this body.
+// A walk that reaches a stub (forest.h EL_STUB) returns 2 (KH_FOUND_UNKNOWN): the nodes listed so
+// far are the resident part of the proof.
 template <typename Hit>
-KH_HD bool prove_walk(const AMap& M, const Recs& R, uint32_t t, const uint64_t* key, Hit hit) {
+KH_HD uint32_t prove_walk(const AMap& M, const Recs& R, uint32_t t, const uint64_t* key, Hit hit) {
   uint32_t d = 0;
   for (int step = 0; step < 70; ++step) {
     const uint32_t r = map_find(M, R, t, d, key);
     if (r == NONE) return false;  // an empty trie, or a branch's empty slot
     const uint32_t db = R.rdb[r];
+    if (db == EL_STUB) {  // the extension above a missing branch is resident (export.h); the branch is not
+      const uint32_t md = R.rmask[r] & 0xFF;
+      if (md > d && (R.rrl[r] == 32 || d == 0)) hit(2ull * r);
+      return (md > d && lcp_nibbles(load_key(key, 0), load_key(R.key(r), 0)) < (int)md) ? 0 : 2;
+    }
     if (R.rrl[r] == 32 || d == 0) hit(2ull * r);
     const uint64_t* L = R.key(r);
     const bool same = L[0] == key[0] && L[1] == key[1] && L[2] == key[2] && L[3] == key[3];

@@ -227,6 +227,54 @@ class _Versioned:
                 continue
             yield from pairs
 
+    # ---- partial handles (from_witness / load_partial): the subtrees a handle lacks are stubs
+    @property
+    def stubs(self):
+        """The live stubs of the handle (kh_trie_stubs); 0 on a handle that holds its tries in full."""
+        n = ctypes.c_uint64()
+        check(lib().kh_trie_stubs(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def missing(self):
+        """[(trie_id, hash)] the last commit, block commit or root_of needed and the handle lacks
+        (kh_trie_missing): what MPTNodeMissingException names in the reference.  Empty unless that
+        call raised MPTNodeMissingException.  trie_id is 0 on a ResidentTrie."""
+        n = ctypes.c_uint64()
+        cap = 0
+        for _ in range(3):
+            tries = np.zeros(max(cap, 1), np.uint32)
+            hs = np.zeros(32 * max(cap, 1), np.uint8)
+            rc = lib().kh_trie_missing(self.h, tries.ctypes.data, hs.ctypes.data, cap, ctypes.byref(n))
+            if rc == _lib.KH_ENOSPC:
+                cap = n.value
+                continue
+            check(rc)
+            return [(int(tries[i]), hs[32 * i:32 * i + 32].tobytes()) for i in range(n.value)]
+        raise RuntimeError("kh_trie_missing: size negotiation failed")
+
+    def fill(self, nodes):
+        """Resolve the stubs whose node is among `nodes` ({hash: encoding} or a list of encodings;
+        kh_trie_fill_nodes); returns the number of nodes decoded into the handle."""
+        encs = list(nodes.values()) if isinstance(nodes, dict) else list(nodes)
+        ed, eo = _pack_dev(encs, self.dev)
+        n = ctypes.c_uint64()
+        self.ctx._sync()
+        check(lib().kh_trie_fill_nodes(self.h, _ptr(ed), _ptr(eo), len(encs), ctypes.byref(n), None))
+        return int(n.value)
+
+    def _need(self, keys, trie_ids):
+        keys = list(keys)
+        n = len(keys)
+        klen = len(keys[0]) if keys else 32
+        kb = np.frombuffer(b"".join(keys) + b"\0", np.uint8).copy()
+        tb = np.asarray(list(trie_ids) + [0], np.uint32) if trie_ids is not None else None
+        flag = np.zeros(max(n, 1), np.uint8)
+        hs = np.zeros(32 * max(n, 1), np.uint8)
+        self.ctx._sync()
+        check(lib().kh_trie_need_host(self.h, tb.ctypes.data if tb is not None else None, kb.ctypes.data, klen, n,
+                                      flag.ctypes.data, hs.ctypes.data))
+        return [hs[32 * i:32 * i + 32].tobytes() if flag[i] else None for i in range(n)]
+
     def nodes_by_hash(self, hashes):
         """getMptNodeByHash over the current version (kh_trie_nodes_by_hash): [encoding or None]
         per 32-byte hash, at most 4096 a call."""
@@ -248,6 +296,20 @@ class _Versioned:
             check(rc)
             return [rl[off[i]:off[i + 1]].tobytes() if found[i] else None for i in range(n)]
         raise RuntimeError("kh_trie_nodes_by_hash: size negotiation failed")
+
+
+class _Unknown:
+    """get's answer for a key whose walk reaches a stub of a partial handle (KH_FOUND_UNKNOWN):
+    neither a value nor None.  Falsy, and equal only to itself."""
+
+    def __bool__(self):
+        return False
+
+    def __repr__(self):
+        return "UNKNOWN"
+
+
+UNKNOWN = _Unknown()
 
 
 class ResidentTrie(_Versioned):
@@ -306,6 +368,37 @@ class ResidentTrie(_Versioned):
         t.h = h
         t.root = bytes(root)
         return t
+
+    @classmethod
+    def from_witness(cls, ctx, root, nodes, hash_keys=False, emit=True):
+        """Open from a root hash and the nodes at hand ({hash: encoding} or a list of encodings: a
+        block's witness; kh_trie_open_partial).  Subtrees whose node is absent become stubs; only a
+        missing root node raises MPTNodeMissingException (its hash in .missing)."""
+        t = cls.__new__(cls)
+        t.ctx, t.dev, t.h = ctx, f"cuda:{ctx.device}", None
+        t.hash_keys = bool(hash_keys)
+        encs = list(nodes.values()) if isinstance(nodes, dict) else list(nodes)
+        ed, eo = _pack_dev(encs, t.dev)
+        h = ctypes.c_void_p()
+        miss = np.zeros(32, np.uint8)
+        flags = (_lib.KH_HASH_KEYS if hash_keys else 0) | (_lib.KH_EMIT_NODES if emit else 0)
+        rb = np.frombuffer(bytes(root), np.uint8).copy()
+        ctx._sync()
+        rc = lib().kh_trie_open_partial(ctx.h, rb.ctypes.data, _ptr(ed), _ptr(eo), len(encs), flags, miss.ctypes.data,
+                                        ctypes.byref(h))
+        if rc == _lib.KH_ENODE:
+            e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+            e.missing = miss.tobytes()
+            raise e
+        check(rc)
+        t.h = h
+        t.root = bytes(root)
+        return t
+
+    def need(self, keys):
+        """[hash or None] per key: the node to fetch before a commit of that key can walk past the
+        stub its path reaches (kh_trie_need_host); None where the path is resident."""
+        return self._need(keys, None)
 
     def _flag(self, hash_keys):
         """The trie's key encoder is fixed at open (as the reference's implicit
@@ -435,7 +528,8 @@ def trie_get(h, keys, trie_ids=None):
             cap = need.value
             continue
         check(rc)
-        return [vals[voff[i]:voff[i + 1]].tobytes() if found[i] else None for i in range(n)]
+        return [UNKNOWN if found[i] == _lib.KH_FOUND_UNKNOWN else vals[voff[i]:voff[i + 1]].tobytes() if found[i]
+                else None for i in range(n)]
     raise RuntimeError("kh_trie_get: size negotiation failed")
 
 
@@ -491,7 +585,8 @@ def trie_prove(h, keys, trie_ids=None, shared=False):
         nn, _, npth = sizes
         table = ProofTable([hs[32 * j:32 * j + 32].tobytes() for j in range(nn)],
                            [rl[int(of[j]):int(of[j + 1])].tobytes() for j in range(nn)], pi[:npth].copy(), po)
-        return [bool(f) for f in found[:len(keys)]], table
+        # (2, KH_FOUND_UNKNOWN: the walk reaches a stub of a partial handle)
+        return [2 if f == _lib.KH_FOUND_UNKNOWN else bool(f) for f in found[:len(keys)]], table
     raise RuntimeError("kh_trie_prove: size negotiation failed")
 
 
@@ -606,8 +701,9 @@ class ResidentForest(_Versioned):
         f.load_nodes(roots, nodes)
         return f
 
-    def load_nodes_raw(self, ids, roots, encs, miss_cap=None):
-        """One kh_forest_load_nodes call: (rc, n_missing, [(list index, hash)] written)."""
+    def load_nodes_raw(self, ids, roots, encs, miss_cap=None, partial=False):
+        """One kh_forest_load_nodes (partial: kh_forest_load_partial) call: (rc, n_missing,
+        [(list index, hash)] written)."""
         ids, roots, encs = list(ids), list(roots), list(encs)
         k = len(ids)
         tb = np.asarray(ids + [0], np.uint32)
@@ -618,12 +714,23 @@ class ResidentForest(_Versioned):
         mh = np.zeros(32 * max(cap, 1), np.uint8)
         nm = ctypes.c_uint64(0)
         self.ctx._sync()
-        rc = lib().kh_forest_load_nodes(self.h, tb.ctypes.data, rb.ctypes.data, k, _ptr(ed), _ptr(eo), len(encs),
-                                        mi.ctypes.data, mh.ctypes.data, cap, ctypes.byref(nm), None)
+        call = lib().kh_forest_load_partial if partial else lib().kh_forest_load_nodes
+        rc = call(self.h, tb.ctypes.data, rb.ctypes.data, k, _ptr(ed), _ptr(eo), len(encs), mi.ctypes.data,
+                  mh.ctypes.data, cap, ctypes.byref(nm), None)
         w = min(int(nm.value), cap)
         return rc, int(nm.value), [(int(mi[e]), mh[32 * e:32 * e + 32].tobytes()) for e in range(w)]
 
-    def load_nodes(self, roots, nodes):
+    def load_partial(self, roots, nodes):
+        """Page tries in from the nodes at hand (kh_forest_load_partial): as load_nodes, but a subtree
+        whose node is absent becomes a stub; only a missing root node raises."""
+        return self.load_nodes(roots, nodes, partial=True)
+
+    def need(self, queries):
+        """queries: [(trie_id, key)] -> [hash or None], as ResidentTrie.need."""
+        q = list(queries)
+        return self._need([k for _, k in q], [t for t, _ in q])
+
+    def load_nodes(self, roots, nodes, partial=False):
         """Page tries in (kh_forest_load_nodes): roots {trie_id: root}, nodes {hash: encoding} or a
         list of encodings.  All or nothing.  Nodes missing from the store raise
         MPTNodeMissingException with .missing = [(trie_id, hash)]: every missing reference of the
@@ -632,7 +739,7 @@ class ResidentForest(_Versioned):
         encs = list(nodes.values()) if isinstance(nodes, dict) else list(nodes)
         cap = max(len(ids), 16)
         for _ in range(2):
-            rc, nm, miss = self.load_nodes_raw(ids, [roots[t] for t in ids], encs, cap)
+            rc, nm, miss = self.load_nodes_raw(ids, [roots[t] for t in ids], encs, cap, partial)
             if rc == _lib.KH_ENODE and nm > cap:
                 cap = nm
                 continue
