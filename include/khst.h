@@ -302,9 +302,22 @@ int kh_trie_open_host(const uint8_t* keys, uint32_t klen, const uint8_t* vals, c
 /* Open a trie from its root hash and a node store: MerklePatriciaTrie.apply(
  * rootHash, source) with getNode (MerklePatriciaTrie.scala:60-66,520-542).  The store holds
  * n node encodings enc[off[i] .. off[i+1]), keyed by their kec256 (content addressed, as
- * NodeStorage is); the nodes reachable from root32 are decoded on the device.  A node
- * missing from the store returns KH_ENODE with its hash in missing32
- * (MPTNodeMissingException); EMPTY_TRIE_HASH opens an empty trie. */
+ * NodeStorage is); the nodes reachable from root32 are decoded on the device.  The open is
+ * kh_forest_load_nodes (below) of the one trie into a fresh handle, so that call's rules hold:
+ *   - KH_EINVAL for a store node on the walk that is not a canonical secure-trie node, by the
+ *     rules of Node.nodeDec and HexPrefix.decode for a 64-nibble key: a branch value anywhere but
+ *     a value-only branch at depth 64, an embedded node of 32 B or more, a path past nibble 64, a
+ *     HexPrefix flag nibble above 3, a non-zero pad nibble, a branch with children starting at
+ *     nibble 64, ...; also for n >= 2^31;
+ *   - KH_ENODE for a node missing from the store (MPTNodeMissingException), with one hash in
+ *     missing32: the first missing one in frontier order of the first round that lacks any (the
+ *     root is round 0; then children in nibble order).  The same store and root report the same
+ *     hash every time;
+ *   - the records come in the load's fixed order, so two opens of the same store give the same
+ *     kh_trie_export_nodes order.
+ * EMPTY_TRIE_HASH opens an empty trie, whatever the store holds.  A failed open leaves no handle.
+ * Device form: d_off non-decreasing (a precondition); the _host form checks that (KH_EINVAL)
+ * before it stages anything. */
 int kh_trie_open_nodes(kh_ctx* ctx, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
                        uint32_t flags, uint8_t missing32[32], kh_trie** out);
 int kh_trie_open_nodes_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,

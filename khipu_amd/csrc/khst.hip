@@ -4005,161 +4005,6 @@ static void map_rebuild(kh_trie* h, uint64_t headroom) {
   h->rdead = h->rn - h->mused;
 }
 
-// one level of the open-from-store walk: decode every frontier node into a record (a
-// leaf, or a branch with the extension above it) and push its children to the next level
-__global__ void __launch_bounds__(BS) k_open_level(OItems I, uint64_t ni, OItems N, NStore S, Recs R,
-                                                   unsigned long long* rcount, uint64_t rbase, uint32_t trie,
-                                                   uint8_t* heap, unsigned long long* heap_n,
-                                                   unsigned long long* leaves, unsigned long long* err,
-                                                   uint8_t* missing) {
-  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
-  if (i >= ni) return;
-  const uint64_t* h = I.ref + 4 * i;
-  const uint8_t* e;
-  uint32_t L;
-  if (I.rl[i] == 32) {
-    const uint64_t p = key_lower_bound(S.hash, S.m, h);
-    if (p >= S.m || key_cmp(S.hash + 4 * p, h) != 0) {  // MPTNodeMissingException (MerklePatriciaTrie.scala:534-537)
-      if (atomicCAS(err, OPEN_OK, OPEN_MISSING) == OPEN_OK)
-        for (int q = 0; q < 32; ++q) missing[q] = (uint8_t)(h[q >> 3] >> (8 * (q & 7)));
-      return;
-    }
-    const uint32_t j = S.idx[p];
-    e = S.enc + S.off[j];
-    L = (uint32_t)(S.off[j + 1] - S.off[j]);
-  } else {
-    e = (const uint8_t*)h;
-    L = I.rl[i];
-  }
-  auto bad = [&](unsigned long long code) { atomicCAS(err, OPEN_OK, code); };
-  RItem top;
-  if (!rlp_valid(e, L, 0, 0) || !rlp_at(e, L, 0, top) || !top.list) return bad(OPEN_BAD);
-  RItem it[18];
-  const int k = rlp_items(e, L, top, it, 18);
-  const uint32_t a = I.a[i], d = I.d[i];
-  uint64_t own[4];  // the node's capped reference (Node.capped, Node.scala:114)
-  uint32_t ownl;
-  if (L >= 32) {
-    for (int q = 0; q < 4; ++q) own[q] = h[q];  // referenced by hash (a root < 32 B: its bytes below)
-    ownl = 32;
-  } else {
-    words_of(e, L, own);
-    ownl = L;
-  }
-  if (L >= 32 && I.rl[i] != 32) return bad(OPEN_BAD);  // an embedded node must be < 32 B
-  const uint64_t* pre = I.pre + 4 * i;
-  auto push = [&](const uint64_t* np, uint32_t na, uint32_t nd, const uint8_t* cref, uint32_t crl, bool is_hash,
-                  const uint64_t* pr, uint32_t prl) {
-    const unsigned long long t = atomicAdd(N.n, 1ULL);
-    if (t >= N.cap) return bad(OPEN_BAD);
-    for (int q = 0; q < 4; ++q) N.pre[4 * t + q] = np[q];
-    N.a[t] = (uint8_t)na;
-    N.d[t] = (uint8_t)nd;
-    uint64_t w[4];
-    words_of(cref, crl, w);
-    for (int q = 0; q < 4; ++q) N.ref[4 * t + q] = w[q];
-    N.rl[t] = (uint8_t)(is_hash ? 32 : crl);
-    for (int q = 0; q < 4; ++q) N.pref[4 * t + q] = pr ? pr[q] : w[q];
-    N.prl[t] = (uint8_t)(pr ? prl : (is_hash ? 32 : crl));
-  };
-  if (k == 17) {  // branch [ref_0 .. ref_15, value]
-    if (it[16].list || it[16].len) {
-      // a secure trie stores a branch value only in khipu's value-only branch (forest.h VB_DEPTH):
-      // no children, at depth 64
-      bool none = !it[16].list && d == VB_DEPTH;
-      for (int c = 0; c < 16 && none; ++c) none = !it[c].list && it[c].len == 0;
-      if (!none) return bad(OPEN_VALUE);
-      const uint64_t vo = atomicAdd(heap_n, (unsigned long long)it[16].len);
-      for (uint32_t q = 0; q < it[16].len; ++q) heap[vo + q] = e[it[16].off + q];
-      const uint64_t r = rbase + atomicAdd(rcount, 1ULL);
-      for (int q = 0; q < 4; ++q) {
-        R.rk[4 * r + q] = pre[q];
-        R.rbref[4 * r + q] = own[q];
-        R.rref[4 * r + q] = I.pref[4 * i + q];
-      }
-      R.rt[r] = trie;
-      R.rd[r] = (uint8_t)a;
-      R.rdb[r] = (uint8_t)VB_DEPTH;
-      R.rvo[r] = vo;
-      R.rvl[r] = it[16].len;
-      R.rbrl[r] = (uint8_t)ownl;
-      R.rrl[r] = I.prl[i];
-      R.rmask[r] = 0;
-      R.rlive[r] = REC_LIVE;
-      atomicAdd(leaves, 1ULL);  // (its key counts as one of the trie's keys)
-      return;
-    }
-    uint32_t mask = 0;
-    for (int c = 0; c < 16; ++c) {
-      if (!it[c].list && it[c].len == 0) continue;
-      if (!it[c].list && it[c].len != 32) return bad(OPEN_BAD);
-      uint64_t np[4] = {pre[0], pre[1], pre[2], pre[3]};
-      set_nibble(np, d, (uint32_t)c);
-      if (!it[c].list) {
-        push(np, d + 1, d + 1, e + it[c].off, 32, true, nullptr, 0);
-      } else {
-        const uint32_t st = c ? it[c - 1].next : top.off;
-        push(np, d + 1, d + 1, e + st, it[c].next - st, false, nullptr, 0);
-      }
-      mask |= 1u << c;
-    }
-    const uint64_t r = rbase + atomicAdd(rcount, 1ULL);
-    for (int q = 0; q < 4; ++q) {
-      R.rk[4 * r + q] = pre[q];
-      R.rbref[4 * r + q] = own[q];
-      R.rref[4 * r + q] = I.pref[4 * i + q];
-    }
-    R.rt[r] = trie;
-    R.rd[r] = (uint8_t)a;
-    R.rdb[r] = (uint8_t)d;
-    R.rvo[r] = 0;
-    R.rvl[r] = 0;
-    R.rbrl[r] = (uint8_t)ownl;
-    R.rrl[r] = I.prl[i];
-    R.rmask[r] = (uint16_t)mask;
-    R.rlive[r] = REC_LIVE;
-    return;
-  }
-  if (k != 2 || it[0].list || it[0].len == 0 || d != a) return bad(OPEN_BAD);  // a leaf / extension hangs where it starts
-  uint8_t nib[64];
-  uint32_t np = 0;
-  bool leaf = false;
-  hp_nibbles(e + it[0].off, it[0].len, &np, &leaf, nib);
-  uint64_t key[4] = {pre[0], pre[1], pre[2], pre[3]};
-  if (d + np > 64) return bad(OPEN_BAD);
-  for (uint32_t q = 0; q < np; ++q) set_nibble(key, d + q, nib[q]);
-  if (leaf) {  // [HP(path, leaf), value]: the key is complete (32-byte keys)
-    if (d + np != 64 || it[1].list) return bad(OPEN_BAD);
-    const uint64_t vo = atomicAdd(heap_n, (unsigned long long)it[1].len);
-    for (uint32_t q = 0; q < it[1].len; ++q) heap[vo + q] = e[it[1].off + q];
-    const uint64_t r = rbase + atomicAdd(rcount, 1ULL);
-    for (int q = 0; q < 4; ++q) {
-      R.rk[4 * r + q] = key[q];
-      R.rbref[4 * r + q] = 0;
-      R.rref[4 * r + q] = I.pref[4 * i + q];
-    }
-    R.rt[r] = trie;
-    R.rd[r] = (uint8_t)a;
-    R.rdb[r] = EL_LEAF;
-    R.rvo[r] = vo;
-    R.rvl[r] = it[1].len;
-    R.rbrl[r] = 0;
-    R.rrl[r] = I.prl[i];
-    R.rmask[r] = 0;
-    R.rlive[r] = REC_LIVE;
-    atomicAdd(leaves, 1ULL);
-    return;
-  }
-  // extension [HP(shared, ext), ref]: its branch child gets the extension's record (anchor a)
-  if (np == 0) return bad(OPEN_BAD);
-  if (!it[1].list) {
-    if (it[1].len != 32) return bad(OPEN_BAD);
-    push(key, a, d + np, e + it[1].off, 32, true, I.pref + 4 * i, I.prl[i]);
-  } else {
-    push(key, a, d + np, e + it[0].next, it[1].next - it[0].next, false, I.pref + 4 * i, I.prl[i]);
-  }
-}
-
 // the (trie id, hash) pairs a refusal kernel listed (k_stub_missing / k_stub_moved) into the
 // handle's missing list: one sync
 static void stub_missing_read(kh_trie* h, const uint32_t* d_trie, const uint64_t* d_hash,
@@ -5861,109 +5706,6 @@ int kh_verify_nodes_packed(const uint8_t* data, const uint64_t* off, uint64_t n,
   })
 }
 
-static OItems oitems_carve(DevBuf& b, uint64_t cap) {
-  Layout L;
-  OItems I{};
-  L.add(I.pre, cap * 4);
-  L.add_all(cap, I.a, I.d);
-  L.add(I.ref, cap * 4);
-  L.add(I.rl, cap);
-  L.add(I.pref, cap * 4);
-  L.add(I.prl, cap);
-  L.add(I.n, 8);
-  place(b, L);
-  I.cap = cap;
-  return I;
-}
-
-// open an (empty) trie from root32 and n stored node encodings (device buffers)
-static void trie_open_nodes(kh_trie* h, const uint8_t* root32, const uint8_t* d_enc, const uint64_t* d_off,
-                            uint64_t n, uint8_t* missing32) {
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  memcpy(h->root, root32, 32);
-  if (memcmp(root32, EMPTY_TRIE_HASH, 32) == 0) return;  // MerklePatriciaTrie.scala:60-66
-  if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "node store too large"};
-  // the store, keyed by kec256 of each encoding (content addressed)
-  Layout L;
-  uint64_t* hs;
-  SortIO S{};
-  unsigned long long* oc;  // records, heap bytes, leaves, error
-  uint8_t* dmiss;
-  L.add(hs, n * 4 + 4);
-  S.declare(L, n, n * 4 + 4, false, n + 1, n + 1, CTR_N);
-  L.add(oc, 8);
-  L.add(dmiss, 64);
-  place(h->ws, L);
-  S.K32 = hs;
-  S.n = n;
-  HIPCHK(hipMemsetAsync(S.ctr, 0, CTR_N * 8, st));
-  HIPCHK(hipMemsetAsync(oc, 0, 64, st));
-  uint64_t total = 0;
-  NStore NS{nullptr, nullptr, 0, d_enc, d_off};
-  if (n) {
-    hipLaunchKernelGGL(k_kec_batch, GRID(n, BS), dim3(BS), 0, st, d_enc, d_off, n, hs);
-    LAUNCH_CHECK();
-    sort_dedup(c, S);
-    NS.hash = S.skey;
-    NS.idx = S.sidx;
-    NS.m = S.m;
-    HIPCHK(hipMemcpyAsync(c->h_pinned, d_off, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 1, d_off + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    total = c->h_pinned[1] - c->h_pinned[0];
-  }
-  // leaf values land in the heap: at most the store's bytes
-  regrow(h->heap, h->heap_n, h->heap_n + total + 64, st);
-  c->h_pinned[0] = h->heap_n;
-  HIPCHK(hipMemcpyAsync(oc + 1, c->h_pinned, 8, hipMemcpyHostToDevice, st));
-  DevBuf fa, fb;
-  OItems cur = oitems_carve(fa, 1);
-  {  // the root: referenced by its hash, at anchor 0
-    uint64_t w[4];
-    memcpy(w, root32, 32);
-    c->h_pinned[1] = 1;
-    HIPCHK(hipMemsetAsync(cur.pre, 0, 32, st));
-    HIPCHK(hipMemsetAsync(cur.a, 0, 1, st));
-    HIPCHK(hipMemsetAsync(cur.d, 0, 1, st));
-    HIPCHK(hipMemcpyAsync(cur.ref, w, 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(cur.pref, w, 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(cur.rl, 32, 1, st));
-    HIPCHK(hipMemsetAsync(cur.prl, 32, 1, st));
-    HIPCHK(hipStreamSynchronize(st));  // w is a host temporary
-  }
-  uint64_t ni = 1, nrec = 0;
-  const uint64_t rn0 = h->rn;
-  for (int level = 0; ni && level < 80; ++level) {
-    h->rn = rn0 + nrec;  // a regrow keeps the records of the earlier levels
-    recs_reserve(h, h->rn + ni + 16);
-    OItems nxt = oitems_carve(level & 1 ? fa : fb, 16 * ni);
-    HIPCHK(hipMemsetAsync(nxt.n, 0, 8, st));
-    hipLaunchKernelGGL(k_open_level, GRID(ni, BS), dim3(BS), 0, st, cur, ni, nxt, NS, recs_of(h), oc, rn0,
-                       0u, (uint8_t*)h->heap.p, oc + 1, oc + 2, oc + 3, dmiss);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, nxt.n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 1, oc, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 8, dmiss, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t code = c->h_pinned[4];
-    if (code == OPEN_MISSING) {
-      if (missing32) memcpy(missing32, c->h_pinned + 8, 32);
-      throw KhError{KH_ENODE, "node missing from the store (MPTNodeMissingException)"};
-    }
-    if (code == OPEN_VALUE) throw KhError{KH_EINVAL, "a branch with a value: not a secure trie"};
-    if (code) throw KhError{KH_EINVAL, "the store holds a node that is not a canonical secure-trie node"};
-    nrec = c->h_pinned[1];
-    ni = c->h_pinned[0];
-    cur = nxt;
-  }
-  if (ni) throw KhError{KH_EINVAL, "node store deeper than a 32-byte key allows"};
-  h->rn = rn0 + nrec;
-  h->heap_n = c->h_pinned[2];
-  h->nleaves += c->h_pinned[3];
-  map_rebuild(h, 1024);
-}
-
 static kh_trie* trie_new(kh_ctx* c, uint32_t flags, bool forest) {
   kh_trie* h = new kh_trie();
   h->c = c;
@@ -6014,53 +5756,6 @@ int kh_trie_open(kh_ctx* c, const uint8_t* d_keys, uint32_t klen, const uint8_t*
     }
     if (root32) memcpy(root32, h->root, 32);
     *out = h;
-  })
-}
-
-int kh_trie_open_nodes(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
-                       uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  if (!c || !out || !root32) return set_err(KH_EINVAL, "null context, root or handle");
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  kh_trie* h = nullptr;
-  API_TRY({
-    HIPCHK(hipSetDevice(c->dev));
-    h = trie_new(c, flags, false);
-    try {
-      trie_open_nodes(h, root32, d_enc, d_off, n, missing32);
-    } catch (...) {
-      delete h;
-      h = nullptr;
-      throw;
-    }
-    *out = h;
-  })
-}
-
-int kh_trie_open_nodes_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
-                            uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  if (!out || !root32 || (n && (!enc || !off))) return set_err(KH_EINVAL, "null input");
-  API_TRY({
-    kh_ctx* c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
-    c->in_vals.ensure(bytes + 64);
-    c->in_voff.ensure((n + 1) * 8 + 64);
-    std::vector<uint64_t> rel(n + 1, 0);
-    for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
-    if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    int rc = kh_trie_open_nodes(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags,
-                                missing32, out);
-    if (rc != KH_OK) return rc;
-    try {
-      make_private(*out);
-    } catch (...) {
-      delete *out;
-      *out = nullptr;
-      throw;
-    }
   })
 }
 
@@ -7134,6 +6829,7 @@ static LItems litems_carve(DevBuf& b, uint64_t cap) {
 // (device buffers) into forest h, beside what it holds.  All or nothing: a refusal or failure
 // before the anchor map is touched leaves no record past the old count (the slots cleared) and
 // every host-side field as it was.  With a savepoint open the map inserts are journaled.
+// A single trie opens the same way (open_store): trie id 0 into a fresh non-forest handle.
 //
 // mode LOAD_PARTIAL (kh_forest_load_partial, kh_trie_open_partial): a hash absent from the store
 // below a root makes a stub (forest.h EL_STUB) instead of ending the round; a missing root is
@@ -7192,23 +6888,23 @@ static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots3
   uint64_t ni = 0;
   uint32_t max_id = 0;
   if (!fill) {
-  if (h->rn && h->mcap) {
-    hipLaunchKernelGGL(k_load_resident, GRID(k, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint32_t*)dtries, k,
-                       tot + 6);
+    if (h->rn && h->mcap) {
+      hipLaunchKernelGGL(k_load_resident, GRID(k, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint32_t*)dtries,
+                         k, tot + 6);
+      LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_load_root_flags, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, rflag);
     LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_load_root_flags, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, rflag);
-  LAUNCH_CHECK();
-  scan_exclusive<uint32_t>(rflag, rpos, k, (uint32_t*)tot, rscr, st);
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[6]) throw KhError{KH_EINVAL, "kh_forest_load_nodes: a listed trie is already resident"};
-  ni = (uint32_t)c->h_pinned[0];
-  for (uint64_t j = 0; j < k; ++j) max_id = std::max(max_id, tries[j]);
-  if (ni == 0) {  // every root is the empty trie's
-    ++h->epoch;
-    return;
-  }
+    scan_exclusive<uint32_t>(rflag, rpos, k, (uint32_t*)tot, rscr, st);
+    HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c->h_pinned[6]) throw KhError{KH_EINVAL, "kh_forest_load_nodes: a listed trie is already resident"};
+    ni = (uint32_t)c->h_pinned[0];
+    for (uint64_t j = 0; j < k; ++j) max_id = std::max(max_id, tries[j]);
+    if (ni == 0) {  // every root is the empty trie's
+      ++h->epoch;
+      return;
+    }
   }
   // the store, keyed by kec256 of each encoding (content addressed)
   Layout L;
@@ -7482,7 +7178,82 @@ static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t
   *n_evicted = ntries;
 }
 
+// a host node store into the context's staging buffers (in_vals, in_voff), checked first:
+// KH_EINVAL before anything is staged
+static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint64_t n) {
+  if (n && !off) return set_err(KH_EINVAL, "null buffer");
+  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
+  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
+  const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
+  c->in_vals.ensure(bytes + 64);
+  c->in_voff.ensure((n + 1) * 8 + 64);
+  std::vector<uint64_t> rel(n + 1, 0);
+  for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
+  if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipStreamSynchronize(c->st));
+  return KH_OK;
+}
+
+// A single trie opened from (root hash, node store on the device): the forest load of the one
+// trie id 0 into a fresh non-forest handle.  LOAD_FULL is kh_trie_open_nodes, LOAD_PARTIAL
+// kh_trie_open_partial.  The first missing node in frontier order (a partial open: only the root)
+// ends the open with KH_ENODE, its hash in missing32; a failed open leaves no handle.  own_ctx: the
+// handle moves to a private context (the *_host entry points; kh_trie_open_partial without one).
+static kh_trie* open_store(kh_ctx* c, const uint8_t* root32, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                           uint32_t flags, uint8_t* missing32, LoadMode mode, bool own_ctx) {
+  if (n && (!d_enc || !d_off)) throw KhError{KH_EINVAL, "null buffer"};
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  HIPCHK(hipSetDevice(c->dev));
+  kh_trie* h = trie_new(c, flags, false);
+  try {
+    const uint32_t id = 0;
+    uint32_t midx = 0;
+    uint8_t m32[32];
+    uint64_t nm = 0;
+    try {
+      forest_load(h, &id, root32, 1, d_enc, d_off, n, &midx, m32, 1, &nm, nullptr, mode);
+    } catch (...) {
+      if (nm && missing32) memcpy(missing32, m32, 32);
+      throw;
+    }
+    memcpy(h->root, root32, 32);
+    if (own_ctx) make_private(h);
+  } catch (...) {
+    delete h;
+    throw;
+  }
+  return h;
+}
+// the same from a host store, staged into the shared context
+static int open_store_host(const uint8_t* root32, const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t flags,
+                           uint8_t* missing32, kh_trie** out, LoadMode mode) {
+  if (!out || !root32 || (n && (!enc || !off))) return set_err(KH_EINVAL, "null input");
+  API_TRY({
+    kh_ctx* c = shared_ctx(current_device());
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->dev));
+    const int rc = stage_store(c, enc, off, n);
+    if (rc != KH_OK) return rc;
+    *out = open_store(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags, missing32, mode,
+                      true);
+  })
+}
+
 extern "C" {
+
+int kh_trie_open_nodes(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
+                       uint32_t flags, uint8_t missing32[32], kh_trie** out) {
+  if (!c || !out || !root32) return set_err(KH_EINVAL, "null context, root or handle");
+  API_TRY({ *out = open_store(c, root32, d_enc, d_off, n, flags, missing32, LOAD_FULL, false); })
+}
+
+int kh_trie_open_nodes_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
+                            uint32_t flags, uint8_t missing32[32], kh_trie** out) {
+  return open_store_host(root32, enc, off, n, flags, missing32, out, LOAD_FULL);
+}
 
 int kh_forest_load_nodes(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
                          const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
@@ -7503,24 +7274,13 @@ int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* 
                               uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
   if (n_missing) *n_missing = 0;
   if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if ((k && (!tries || !roots32)) || (n && !off) || (miss_cap && (!miss_idx || !miss32)))
-    return set_err(KH_EINVAL, "null buffer");
-  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
-  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
+  if ((k && (!tries || !roots32)) || (miss_cap && (!miss_idx || !miss32))) return set_err(KH_EINVAL, "null buffer");
   API_TRY({
     HANDLE_LOCK(f);
     kh_ctx* c = f->c;
     HIPCHK(hipSetDevice(c->dev));
-    const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
-    c->in_vals.ensure(bytes + 64);
-    c->in_voff.ensure((n + 1) * 8 + 64);
-    std::vector<uint64_t> rel(n + 1, 0);
-    for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
-    if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
+    const int rc = stage_store(c, enc, off, n);
+    if (rc != KH_OK) return rc;
     forest_load(f, tries, roots32, k, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, miss_idx, miss32,
                 miss_cap, n_missing, stats);
   })
@@ -7616,77 +7376,20 @@ int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8
 }
 
 // ---- partial handles: open / load from a witness, fill, and what a refused commit needs
-// a host node store into the context's staging buffers (in_vals, in_voff); checks as the host loads
-static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint64_t n) {
-  if (n && !off) return set_err(KH_EINVAL, "null buffer");
-  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
-  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
-  const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
-  c->in_vals.ensure(bytes + 64);
-  c->in_voff.ensure((n + 1) * 8 + 64);
-  std::vector<uint64_t> rel(n + 1, 0);
-  for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
-  if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipStreamSynchronize(c->st));
-  return KH_OK;
-}
-
 int kh_trie_open_partial(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
                          uint32_t flags, uint8_t missing32[32], kh_trie** out) {
   if (!out || !root32) return set_err(KH_EINVAL, "null root or handle");
-  if (n && (!d_enc || !d_off)) return set_err(KH_EINVAL, "null buffer");
-  const bool host = !c;  // (as kh_forest_open: the context the *_host entry points use, a private handle)
-  kh_trie* h = nullptr;
   API_TRY({
-    if (!c) c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    h = trie_new(c, flags, false);
-    try {  // the forest load with the one trie id 0 (a missing root: KH_ENODE, its hash in missing32)
-      const uint32_t id = 0;
-      uint32_t midx = 0;
-      uint8_t m32[32];
-      uint64_t nm = 0;
-      try {
-        forest_load(h, &id, root32, 1, d_enc, d_off, n, &midx, m32, 1, &nm, nullptr, LOAD_PARTIAL);
-      } catch (...) {
-        if (nm && missing32) memcpy(missing32, m32, 32);
-        throw;
-      }
-      memcpy(h->root, root32, 32);
-      if (host) make_private(h);
-    } catch (...) {
-      delete h;
-      h = nullptr;
-      throw;
-    }
-    *out = h;
+    // (no context, as kh_forest_open: the one the *_host entry points use, and a private handle)
+    const bool host = !c;
+    if (host) c = shared_ctx(current_device());
+    *out = open_store(c, root32, d_enc, d_off, n, flags, missing32, LOAD_PARTIAL, host);
   })
 }
 
 int kh_trie_open_partial_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
                               uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  if (!out || !root32 || (n && (!enc || !off))) return set_err(KH_EINVAL, "null input");
-  API_TRY({
-    kh_ctx* c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    int rc = stage_store(c, enc, off, n);
-    if (rc != KH_OK) return rc;
-    rc = kh_trie_open_partial(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags,
-                              missing32, out);
-    if (rc != KH_OK) return rc;
-    try {
-      make_private(*out);
-    } catch (...) {
-      delete *out;
-      *out = nullptr;
-      throw;
-    }
-  })
+  return open_store_host(root32, enc, off, n, flags, missing32, out, LOAD_PARTIAL);
 }
 
 int kh_forest_load_partial(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,

@@ -1,5 +1,7 @@
 // Forest load: many tries decoded from one node store into a resident forest, beside what it
-// holds (kh_forest_load_nodes), and the bodies of kh_forest_roots / kh_forest_evict.
+// holds (kh_forest_load_nodes), and the bodies of kh_forest_roots / kh_forest_evict.  The open of
+// a single trie from a node store (kh_trie_open_nodes, kh_trie_open_partial) is this load with
+// the one trie id 0: there is no other walk.
 //
 // The walk is level-synchronous, the listed roots being round 0.  One round over a frontier of
 // ni items (an item is one node to decode: referenced by hash and looked up in the store, or
@@ -15,17 +17,17 @@
 //
 // load_node is the decode, shared by both passes through a sink (LoadCount / LoadFill), by the
 // kernels of load_kernels.hip and by the host replay of tests/load_host.  The per-node rules are
-// those of the single-trie open (k_open_level), with what that walk leaves to its callers made
-// explicit: an embedded node must be shorter than 32 bytes where it is pushed, a branch with
-// children cannot start at nibble 64, and a HexPrefix flag nibble is 0..3 with a zero pad nibble.
-// The items of a node are walked in order: there is no array of 18 items and no array of 64
-// nibbles per thread (k_open_level keeps both, indexed at run time, in scratch memory).
+// those of Node.nodeDec and HexPrefix.decode for a 64-nibble key: an embedded node must be shorter
+// than 32 bytes where it is pushed, a branch with children cannot start at nibble 64, and a
+// HexPrefix flag nibble is 0..3 with a zero pad nibble.  The items of a node are walked in order:
+// there is no array of 18 items and no array of 64 nibbles per thread, so nothing is indexed at
+// run time in scratch memory.
 #pragma once
 #include "forest.h"
 
 namespace khst {
 
-// a frontier: OItems plus the list index of the trie each item belongs to
+// a frontier: one item per node to decode, with the list index of the trie it belongs to
 struct LItems {
   uint64_t* pre;   // [cap*4] key prefix: nibbles [0, d) of every key below
   uint8_t* a;      // anchor depth of the record the node belongs to

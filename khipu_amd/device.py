@@ -344,36 +344,9 @@ class ResidentTrie(_Versioned):
         self.root = root.tobytes()
 
     @classmethod
-    def from_nodes(cls, ctx, root, nodes, hash_keys=False, emit=True):
-        """Open from a root hash and a node store {hash: encoding} (kh_trie_open_nodes;
-        MerklePatriciaTrie.apply(rootHash, source)).  A missing node raises
-        MPTNodeMissingException with the missing hash in .missing."""
-        t = cls.__new__(cls)
-        t.ctx, t.dev, t.h = ctx, f"cuda:{ctx.device}", None
-        t.hash_keys = bool(hash_keys)
-        encs = list(nodes.values())
-        ed, eo = _pack_dev(encs, t.dev)
-        h = ctypes.c_void_p()
-        miss = np.zeros(32, np.uint8)
-        flags = (_lib.KH_HASH_KEYS if hash_keys else 0) | (_lib.KH_EMIT_NODES if emit else 0)
-        rb = np.frombuffer(bytes(root), np.uint8).copy()
-        ctx._sync()
-        rc = lib().kh_trie_open_nodes(ctx.h, rb.ctypes.data, _ptr(ed), _ptr(eo), len(encs), flags, miss.ctypes.data,
-                                      ctypes.byref(h))
-        if rc == _lib.KH_ENODE:
-            e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
-            e.missing = miss.tobytes()
-            raise e
-        check(rc)
-        t.h = h
-        t.root = bytes(root)
-        return t
-
-    @classmethod
-    def from_witness(cls, ctx, root, nodes, hash_keys=False, emit=True):
-        """Open from a root hash and the nodes at hand ({hash: encoding} or a list of encodings: a
-        block's witness; kh_trie_open_partial).  Subtrees whose node is absent become stubs; only a
-        missing root node raises MPTNodeMissingException (its hash in .missing)."""
+    def _from_store(cls, open_fn, ctx, root, nodes, hash_keys, emit):
+        """A handle opened by open_fn (kh_trie_open_nodes or kh_trie_open_partial: one signature)
+        from a root hash and node encodings ({hash: encoding} or a list)."""
         t = cls.__new__(cls)
         t.ctx, t.dev, t.h = ctx, f"cuda:{ctx.device}", None
         t.hash_keys = bool(hash_keys)
@@ -384,8 +357,7 @@ class ResidentTrie(_Versioned):
         flags = (_lib.KH_HASH_KEYS if hash_keys else 0) | (_lib.KH_EMIT_NODES if emit else 0)
         rb = np.frombuffer(bytes(root), np.uint8).copy()
         ctx._sync()
-        rc = lib().kh_trie_open_partial(ctx.h, rb.ctypes.data, _ptr(ed), _ptr(eo), len(encs), flags, miss.ctypes.data,
-                                        ctypes.byref(h))
+        rc = open_fn(ctx.h, rb.ctypes.data, _ptr(ed), _ptr(eo), len(encs), flags, miss.ctypes.data, ctypes.byref(h))
         if rc == _lib.KH_ENODE:
             e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
             e.missing = miss.tobytes()
@@ -394,6 +366,20 @@ class ResidentTrie(_Versioned):
         t.h = h
         t.root = bytes(root)
         return t
+
+    @classmethod
+    def from_nodes(cls, ctx, root, nodes, hash_keys=False, emit=True):
+        """Open from a root hash and a node store {hash: encoding} (kh_trie_open_nodes;
+        MerklePatriciaTrie.apply(rootHash, source)).  A missing node raises
+        MPTNodeMissingException with the missing hash in .missing."""
+        return cls._from_store(lib().kh_trie_open_nodes, ctx, root, nodes, hash_keys, emit)
+
+    @classmethod
+    def from_witness(cls, ctx, root, nodes, hash_keys=False, emit=True):
+        """Open from a root hash and the nodes at hand ({hash: encoding} or a list of encodings: a
+        block's witness; kh_trie_open_partial).  Subtrees whose node is absent become stubs; only a
+        missing root node raises MPTNodeMissingException (its hash in .missing)."""
+        return cls._from_store(lib().kh_trie_open_partial, ctx, root, nodes, hash_keys, emit)
 
     def need(self, keys):
         """[hash or None] per key: the node to fetch before a commit of that key can walk past the

@@ -12,6 +12,10 @@ library's own HIP-event time (kh_stats.t_total_ms and its split).  Medians of --
           exported once as the store, loaded into a fresh forest: nodes/s and the split into
           store hashing + sort, rounds, anchor map.
   evict   half of --resident tries evicted, then kh_trie_compact.
+  open    (not in the default legs) kh_trie_open_nodes, the store already in HBM, wall clock around
+          the call, the handle freed after each: on the exported store of one trie of --slots
+          slots and of a state trie of each of --open-accounts synthetic accounts.  A size whose
+          open fails (out of memory) is recorded with its error.
 One JSON object; nothing here is gated."""
 import argparse
 import ctypes
@@ -36,12 +40,13 @@ def main():
     ap.add_argument("--resume-tries", type=int, default=10_000)
     ap.add_argument("--resume-reps", type=int, default=3)
     ap.add_argument("--cfg", type=int, default=4)
+    ap.add_argument("--open-accounts", default="1000000,10000000")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     import torch
     from khipu_amd import _lib
     from khipu_amd._lib import KhStats, check, lib
-    from khipu_amd.device import Ctx, ResidentForest, _ptr
+    from khipu_amd.device import Ctx, ResidentForest, ResidentTrie, _ptr
     ctx = Ctx(0)
     dev = "cuda:0"
     g = torch.Generator(device=dev)
@@ -204,6 +209,43 @@ def main():
         s = summary(runs[1:])
         res["resume"] = dict(s, tries=len(ids), slots=nslots, store_nodes=n, store_bytes=int(enc.size), records=recs,
                              export_s=round(export_s, 3), nodes_per_s=round(n / (s["wall_ms_median"] / 1e3)))
+    if "open" in legs:
+        def open_leg(src, root, nkeys, flags):
+            enc, off = export_store(src)
+            src.close()
+            n = len(off) - 1
+            d_enc, d_off = to_dev(enc, off)
+            rb = np.frombuffer(root, np.uint8).copy()
+            miss = np.zeros(32, np.uint8)
+            leg = {"keys": nkeys, "store_nodes": n, "store_bytes": int(enc.size)}
+            ms = []
+            for _ in range(a.reps + 1):  # (the first run sizes the workspaces: dropped)
+                h = ctypes.c_void_p()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                rc = lib().kh_trie_open_nodes(ctx.h, rb.ctypes.data, _ptr(d_enc), _ptr(d_off), n, flags,
+                                              miss.ctypes.data, ctypes.byref(h))
+                ms.append((time.perf_counter() - t0) * 1e3)
+                if rc != _lib.KH_OK:
+                    leg["error"] = [rc, lib().kh_last_error().decode(errors="replace")]
+                    return leg
+                size = ctypes.c_uint64()
+                check(lib().kh_trie_size(h, ctypes.byref(size)))
+                assert size.value == nkeys
+                lib().kh_trie_free(h)
+            leg.update(wall_ms_median=med(ms[1:]), wall_ms_min=round(min(ms[1:]), 3), wall_ms_max=round(max(ms[1:]), 3))
+            return leg
+
+        res["open"] = {}
+        one = random_forest(0, 1, a.slots)
+        res["open"][f"slots_{a.slots}"] = open_leg(one, one.roots()[0], a.slots, 0)
+        for n in [int(x) for x in a.open_accounts.split(",") if x]:
+            addr, vals, voff = ctx.synth_accounts(9, 0, n)
+            t = ResidentTrie.__new__(ResidentTrie)
+            t.ctx, t.dev, t.h = ctx, dev, None
+            t._open(addr, 20, vals, voff, n, True, emit=False)
+            del addr, vals, voff
+            res["open"][f"accounts_{n}"] = open_leg(t, t.root, n, _lib.KH_HASH_KEYS)
     line = json.dumps(res)
     print(line)
     if a.out:

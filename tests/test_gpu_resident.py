@@ -330,6 +330,217 @@ def test_open_from_node_store(khst, oracle, sc):
         assert ei.value.missing == victim
 
 
+def _oracle_trie(oracle, ks, vs, blocks=()):
+    o = oracle.Trie()
+    for k, v in zip(ks, vs):
+        o.put(k, v)
+    for ups, dels in blocks:
+        for k, v in ups:
+            o.put(k, v)
+        for k in dels:
+            o.remove(k)
+    return o
+
+
+def _open_raw(ctx, root, encs):
+    """kh_trie_open_nodes itself: (rc, handle value or None, missing32)."""
+    import ctypes
+    from khipu_amd._lib import lib
+    from khipu_amd.device import _pack_dev, _ptr
+    ed, eo = _pack_dev(list(encs), f"cuda:{ctx.device}")
+    h = ctypes.c_void_p()
+    miss = np.zeros(32, np.uint8)
+    rb = np.frombuffer(bytes(root), np.uint8).copy()
+    ctx._sync()
+    rc = lib().kh_trie_open_nodes(ctx.h, rb.ctypes.data, _ptr(ed), _ptr(eo), len(encs), 0, miss.ctypes.data,
+                                  ctypes.byref(h))
+    return rc, h.value, miss.tobytes()
+
+
+def _open_stores(oracle):
+    """(name, oracle trie) of the stores the open is checked on against the forest load."""
+    from tests import export_cases, proof_cases
+    out = [(sc[0], _oracle_trie(oracle, sc[1], sc[2])) for sc in C.commit_scenarios()[:4]]
+    r = random.Random(41)
+    out.append(("one_key", _oracle_trie(oracle, [C._rk(r)], [C.account_value(r)])))
+    out.append(("embedded", _oracle_trie(oracle, *export_cases.embedded_case())))
+    for small in (False, True):  # khipu's value-only branch, hashed and embedded in its parent
+        ks, vs, blocks, _ = proof_cases.vb_case(small)
+        out.append((f"value_only_branch_{'inline' if small else 'hashed'}", _oracle_trie(oracle, ks, vs, blocks[:1])))
+    return out
+
+
+def test_open_is_the_forest_load(khst, oracle):
+    """kh_trie_open_nodes is kh_forest_load_nodes of the one trie id 0: both handles export the
+    same (hash, encoding) sequence, in the same order, and it is the oracle's reachable() set."""
+    from khipu_amd.device import Ctx, ResidentForest, ResidentTrie
+    ctx = Ctx(0)
+    for name, o in _open_stores(oracle):
+        root = o.root_hash()
+        store = o.reachable()
+        t = ResidentTrie.from_nodes(ctx, root, store)
+        f = ResidentForest.from_nodes(ctx, {0: root}, store)
+        (troot, tnodes), (froots, fnodes) = t.checkpoint(), f.checkpoint()
+        assert troot == root and froots == {0: root}, name
+        assert list(tnodes.items()) == list(fnodes.items()), name
+        assert tnodes == store, name
+        assert len(t) == len(f), name
+        t.close()
+        f.close()
+
+
+def test_open_order_is_deterministic(khst, oracle):
+    """The same store in two shuffled orders, with duplicates and 30 unrelated nodes, opened twice
+    each: one export order."""
+    from khipu_amd.device import Ctx, ResidentTrie
+    ctx = Ctx(0)
+    r = random.Random(42)
+    ks = [C._rk(r) for _ in range(300)]
+    o = _oracle_trie(oracle, ks, [C.storage_value(r) if i % 3 else C.account_value(r) for i in range(300)])
+    sk = [C._rk(r) for _ in range(40)]
+    stranger = list(_oracle_trie(oracle, sk, [C.account_value(r) for _ in sk]).reachable().values())[:30]
+    assert len(stranger) == 30
+    encs = list(o.reachable().values())
+    encs = encs + encs[::3] + stranger
+    orders = []
+    for _ in range(2):
+        r.shuffle(encs)
+        for _ in range(2):
+            t = ResidentTrie.from_nodes(ctx, o.root_hash(), list(encs))
+            orders.append(list(t.export_nodes()))
+            t.close()
+    assert dict(orders[0]) == o.reachable() and len(orders[0]) == len(o.reachable())
+    assert all(x == orders[0] for x in orders[1:])
+
+
+def _malformed_stores(oracle):
+    """(name, root, store): each root names a node the open must refuse with KH_EINVAL, in a store
+    beside a good 60-key trie."""
+    from tests import export_cases
+    from tests.test_load_host import _lst, _s, malformed_roots
+    r = random.Random(3)
+    ks = [C._rk(r) for _ in range(60)]
+    good = list(_oracle_trie(oracle, ks, [C.account_value(r) for _ in ks]).reachable().values())
+    bad = [(n, e) for n, e, _ in malformed_roots()]
+    assert any(n == "hp_flag_4" for n, _ in bad)
+    # a leaf whose even flag comes with a non-zero pad nibble
+    bad.append(("leaf_pad_nibble", _lst([_s(b"\x21" + b"\x11" * 32), _s(b"value" * 8)])))
+    out = [(n, oracle.kec256(e), good + [e]) for n, e in bad]
+    # a branch at depth 64 with a child: a one-key trie's root leaf rewritten into an extension over
+    # all 64 nibbles, whose child is a branch holding one hash reference
+    key = C._rk(r)
+    leaf = _oracle_trie(oracle, [key], [b"value" * 8])
+    root = leaf.reachable()[leaf.root_hash()]
+    _, q, m = export_cases._items(root)[0]
+    assert m == 33 and root[q] == 0x20 and root[q + 1:q + m] == key  # HP(64 nibbles, leaf)
+    branch = _lst([_s(b"\x77" * 32)] + [b"\x80"] * 16)
+    ext = _lst([_s(b"\x00" + key), _s(oracle.kec256(branch))])
+    out.append(("branch_at_depth_64", oracle.kec256(ext), good + [ext, branch]))
+    # a bad leaf below the root of a 300-key trie: the rounds before it had written records
+    ks = [C._rk(r) for _ in range(300)]
+    o = _oracle_trie(oracle, ks, [C.account_value(r) for _ in ks])
+    enc = dict(o.reachable())
+    top = enc[o.root_hash()]
+    _, q, m = next(it for it in export_cases._items(top)[:16] if not it[0] and it[2] == 32)
+    leaf2 = _lst([_s(b"\x31" + b"\x11" * 32), _s(b"value" * 8)])  # its path runs past nibble 64
+    top2 = top[:q] + oracle.kec256(leaf2) + top[q + m:]
+    out.append(("bad_leaf_below_the_root", oracle.kec256(top2),
+                [e for h, e in enc.items() if h != o.root_hash()] + [top2, leaf2]))
+    return out
+
+
+def test_open_refuses_malformed_stores(khst, oracle):
+    """The open applies the load's decode rules (those of HexPrefix.decode and of a 64-nibble key):
+    KH_EINVAL and no handle, whatever else the store holds."""
+    from khipu_amd import _lib
+    from khipu_amd._lib import MPTException
+    from khipu_amd.device import Ctx, ResidentTrie
+    ctx = Ctx(0)
+    cases = _malformed_stores(oracle)
+    assert {"hp_flag_4", "leaf_pad_nibble", "branch_at_depth_64", "bad_leaf_below_the_root"} <= {n for n, _, _ in cases}
+    for name, root, store in cases:
+        rc, h, _ = _open_raw(ctx, root, store)
+        assert rc == _lib.KH_EINVAL and h is None, name
+        with pytest.raises(MPTException) as ei:
+            ResidentTrie.from_nodes(ctx, root, store)
+        assert ei.value.code == _lib.KH_EINVAL, name
+
+
+def test_open_reports_the_first_missing_node(khst, oracle):
+    """Two hash children of the root absent, in different nibbles: the one in the lower nibble is
+    reported, every time.  No store at all: the root is reported, or the empty trie opens."""
+    from khipu_amd import _lib
+    from khipu_amd.device import Ctx, ResidentTrie
+    from tests import export_cases
+    from tests.writeback import EMPTY_TRIE_HASH
+    ctx = Ctx(0)
+    r = random.Random(43)
+    ks = [C._rk(r) for _ in range(300)]
+    o = _oracle_trie(oracle, ks, [C.account_value(r) for _ in ks])
+    store = o.reachable()
+    top = store[o.root_hash()]
+    kids = [top[q:q + m] for l, q, m in export_cases._items(top)[:16] if not l and m == 32]  # (nibble order)
+    assert len(kids) >= 2
+    lo, hi = kids[1], kids[-1]
+    encs = [e for h, e in store.items() if h not in (lo, hi)]
+    assert len(encs) == len(store) - 2
+    for _ in range(2):
+        rc, h, miss = _open_raw(ctx, o.root_hash(), encs)
+        assert rc == _lib.KH_ENODE and h is None and miss == lo
+    rc, h, miss = _open_raw(ctx, o.root_hash(), [])
+    assert rc == _lib.KH_ENODE and h is None and miss == o.root_hash()
+    t = ResidentTrie.from_nodes(ctx, EMPTY_TRIE_HASH, {})
+    assert len(t) == 0 and t.get_root() == EMPTY_TRIE_HASH
+    t.close()
+
+
+def test_open_nodes_host_entry(khst, oracle):
+    """kh_trie_open_nodes_host: a decreasing offset pair is KH_EINVAL before anything is staged, no
+    handle written; a good store opens to the root and the first commit root of the device entry."""
+    import ctypes
+    from khipu_amd import _lib
+    from khipu_amd._lib import check, lib
+    from khipu_amd.device import Ctx, ResidentTrie
+    r = random.Random(44)
+    ks = [C._rk(r) for _ in range(200)]
+    o = _oracle_trie(oracle, ks, [C.account_value(r) for _ in ks])
+    root = o.root_hash()
+    encs = list(o.reachable().values())
+    eb = np.frombuffer(b"".join(encs) + bytes(8), np.uint8).copy()
+    eo = np.concatenate([[0], np.cumsum([len(e) for e in encs])]).astype(np.uint64)
+    rb = np.frombuffer(root, np.uint8).copy()
+    miss = np.zeros(32, np.uint8)
+    h = ctypes.c_void_p()
+    bad = eo.copy()
+    bad[5] = bad[4] - 1
+    rc = lib().kh_trie_open_nodes_host(rb.ctypes.data, eb.ctypes.data, bad.ctypes.data, len(encs), 0, miss.ctypes.data,
+                                       ctypes.byref(h))
+    assert rc == _lib.KH_EINVAL and h.value is None
+    check(lib().kh_trie_open_nodes_host(rb.ctypes.data, eb.ctypes.data, eo.ctypes.data, len(encs), 0, miss.ctypes.data,
+                                        ctypes.byref(h)))
+    assert h.value is not None
+    ctx = Ctx(0)
+    d = ResidentTrie.from_nodes(ctx, root, encs)
+    got = np.zeros(32, np.uint8)
+    check(lib().kh_trie_root_of(h, None, None, None, 0, None, 0, 32, 0, got.ctypes.data, None))
+    assert got.tobytes() == d.get_root() == root
+    ups = [(ks[0], C.account_value(r)), (C._rk(r), C.account_value(r))]
+    dels = [ks[1]]
+    uk = np.frombuffer(b"".join(k for k, _ in ups), np.uint8).copy()
+    uv = np.frombuffer(b"".join(v for _, v in ups) + bytes(8), np.uint8).copy()
+    uo = np.concatenate([[0], np.cumsum([len(v) for _, v in ups])]).astype(np.uint64)
+    dk = np.frombuffer(b"".join(dels), np.uint8).copy()
+    check(lib().kh_trie_apply_host(h, uk.ctypes.data, uv.ctypes.data, uo.ctypes.data, len(ups), dk.ctypes.data,
+                                   len(dels), 32, 0, got.ctypes.data, None))
+    for k, v in ups:
+        o.put(k, v)
+    for k in dels:
+        o.remove(k)
+    assert got.tobytes() == d.commit(ups, dels) == o.root_hash()
+    d.close()
+    lib().kh_trie_free(h)
+
+
 def test_open_from_node_store_1m(khst, oracle):
     """At 1M accounts: the node set a resident trie writes back at open, opened again from
     the root alone, gives the same roots through the same commits."""
