@@ -3563,9 +3563,13 @@ __global__ void __launch_bounds__(GATHER_BS) k_f_gather(AMap M, Recs R, const ui
 
 // after the element build (c->T): one new record per branch (+ extension) at base + j,
 // and the write-back selection of branch / extension j (node m + 2j, m + 2j + 1): a node
-// identical to the one the old version holds at the same anchor is not written back
+// identical to the one the old version holds is not written back.  The old version holds the
+// branch at the same anchor unless its extension was re-cut (a branch above it went or came
+// while an op walked into this one and left it as it was, the delete of an absent key): with a
+// write-back set to keep (emit), the old branch at depth db on the key's path is then found by
+// the walk from the root, and only the new extension is written back.
 __global__ void __launch_bounds__(BS) k_f_branch_recs(Topo T, const uint32_t* Bp, const uint32_t* tries, AMap M,
-                                                      Recs R, uint64_t base, uint8_t* sel) {
+                                                      Recs R, uint64_t base, uint8_t* sel, bool emit) {
   const uint64_t j = (uint64_t)blockIdx.x * BS + threadIdx.x;
   if (j >= *Bp) return;
   const uint64_t f = T.br_first[j], r = base + j;
@@ -3593,12 +3597,24 @@ __global__ void __launch_bounds__(BS) k_f_branch_recs(Topo T, const uint32_t* Bp
   v.vl = 0;
   v.vo = 0;
   rec_store(R.rk.b, r, v);
-  const uint32_t old = map_find(M, R, t, d, K);
+  uint32_t old = map_find(M, R, t, d, K);
+  if (emit && (old == NONE || R.rdb[old] != db)) {
+    old = NONE;
+    for (uint32_t dc = 0, step = 0; step < 70; ++step) {
+      const uint32_t r0 = map_find(M, R, t, dc, K);
+      if (r0 == NONE) break;
+      const uint32_t b0 = R.rdb[r0];  // (EL_LEAF, EL_STUB and VB_DEPTH are past every branch depth)
+      const bool on_path = b0 <= db && lcp_nibbles(load_key(K, 0), load_key(R.key(r0), 0)) >= (int)b0;
+      if (on_path && b0 == db) old = r0;
+      if (!on_path || b0 == db) break;
+      dc = b0 + 1;
+    }
+  }
   bool same_b = false, same_x = false;
   if (old != NONE && R.rdb[old] == db && R.rbrl[old] == brl) {
     same_b = true;
     for (int q = 0; q < 4; ++q) same_b = same_b && R.rbref[4ull * old + q] == T.br_ref[4 * j + q];
-    same_x = same_b && R.rrl[old] == xrl;
+    same_x = same_b && R.rd[old] == d && R.rrl[old] == xrl;
     for (int q = 0; q < 4; ++q) same_x = same_x && R.rref[4ull * old + q] == xr[q];
   }
   sel[T.m + 2 * j] = same_b ? 0 : 1;
@@ -4501,7 +4517,7 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     Topo T = c->T;
     if (B)
       hipLaunchKernelGGL(k_f_branch_recs, GRID(B, BS), dim3(BS), 0, st, T, (const uint32_t*)(T.ctr + CTR_B),
-                         (const uint32_t*)tries, M, R, base_b, sel);
+                         (const uint32_t*)tries, M, R, base_b, sel, keep_em);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_f_elem_flags, GRID(m, BS), dim3(BS), 0, st, T, E, (const uint32_t*)h->touched.p, sel, isnew,
                        esrc, rein);

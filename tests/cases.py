@@ -163,6 +163,14 @@ def commit_scenarios(seed=21):
     vs = [acct() for _ in ks]
     out.append(("large_batch", ks, vs, [([(k, acct()) for k in r.sample(ks, 700)] + [(_rk(r), acct()) for _ in range(300)],
                                          r.sample(ks, 500))]))
+    # a branch that an op walks into and leaves as it is (the delete of an absent key) while the
+    # branch above it goes, so its extension is re-cut and its record re-anchored, then comes back:
+    # the branch's node is unchanged both times, and only the new extension belongs in the write-back
+    # set (found by tests/test_gpu_commit_fuzz.py, forest seed 201, step 36)
+    k1, k2, k3 = b"\x11" + _rk(r)[1:], b"\x12" + _rk(r)[1:], b"\x25" + _rk(r)[1:]
+    absent = [b"\x13" + _rk(r)[1:], b"\x14" + _rk(r)[1:]]
+    out.append(("recut_opened_branch", [k1, k2, k3], [acct(), acct(), acct()],
+                [([], [k3, absent[0]]), ([(k3, acct())], [absent[1]])]))
     return out
 
 
