@@ -605,6 +605,10 @@ int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8
  * When any capacity is short: KH_ENOSPC, and only *n_nodes, *rlp_len and *n_path are written (a
  * retry with exactly those sizes succeeds). */
 #define KH_PROVE_SHARED 0x1u
+/* KH_PROVE_TRIE_KEYS: the keys are trie keys already (klen == 32; on a KH_HASH_KEYS handle the
+ * kec256 values a range scan returns) and are not hashed.  kh_verify_proofs with flags = 0 checks
+ * such proofs. */
+#define KH_PROVE_TRIE_KEYS 0x2u
 int kh_trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
                   uint32_t flags, uint8_t* found,
                   uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off,
@@ -633,6 +637,34 @@ int kh_verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t* key
                      uint32_t flags, const uint8_t* rlp, const uint64_t* off, uint64_t n_nodes,
                      const uint32_t* path_idx, const uint64_t* path_off,
                      uint8_t* status, uint8_t* vals, uint64_t val_cap, uint64_t* voff, uint64_t* val_bytes);
+
+/* ---- range scan: a resident trie read in key order ----
+ * The first entries of [origin32, limit32] (both inclusive; NULL = 32 zero bytes / 32 bytes of 0xFF;
+ * origin > limit: an empty answer) of trie `trie` (forests; ignored on a single trie; an id the
+ * forest does not hold: an empty answer) in ascending key order: at most max_entries, with values
+ * fitting val_cap.  Keys are TRIE keys: on a KH_HASH_KEYS handle the kec256 values (preimages
+ * are not kept).  keys32 holds 32 * max_entries bytes, voff max_entries + 1 slots; entry i is
+ * keys32[32i..) with the value vals[voff[i]..voff[i+1]).  *more = 1 and next32 = the first key not
+ * returned when one exists in range (continue with origin = next32), else *more = 0.  No cursor
+ * and no epoch: a call reads the current version (with a savepoint open, the commits since), and
+ * is read-only on the handle.  Work and memory follow max_entries, not the trie's size
+ * (khipu_amd/csrc/range.h).
+ *   KH_ENOSPC  even the first entry's value does not fit: *val_bytes is its size, nothing else
+ *              is written
+ *   KH_EINVAL  max_entries == 0 or >= 2^31, or a null output
+ *   KH_ENODE   (partial handles only) a missing subtree is among the first max_entries + 1 things
+ *              in range, a missing subtree that meets the range counting as one thing at its
+ *              lowest key: missing32 (nullable) is the hash of its node, nothing else is written
+ * _host form with host buffers; kh_dev_trie_range with keys32 / vals / voff device buffers, on the
+ * handle's context stream (the scalar outputs are host words, valid on return). */
+int kh_trie_range_host(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                       uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
+                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32],
+                       uint8_t missing32[32]);
+int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                      uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
+                      uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32],
+                      uint8_t missing32[32]);
 
 /* HBM held by a resident trie or forest.  Records and the value heap are append-only between
  * compactions: a commit appends the records and values it makes and leaves the ones it

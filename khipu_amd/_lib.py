@@ -24,6 +24,7 @@ KH_NO_TRIE = 0xFFFFFFFF
 KH_EXPORT_VERIFY = 0x1  # kh_trie_export_nodes: re-hash every encoding against its cached reference
 KH_FOUND_UNKNOWN = 2  # kh_trie_get / kh_trie_prove: the key's walk reaches a stub of a partial handle
 KH_PROVE_SHARED = 0x1  # kh_trie_prove: every (record, node) once in the table (a block witness)
+KH_PROVE_TRIE_KEYS = 0x2  # kh_trie_prove: the keys are trie keys already (a range scan's), not hashed
 # kh_verify_proofs statuses
 KH_PROOF_ABSENT = 0     # valid: the key is not in the trie
 KH_PROOF_VALUE = 1      # valid: the value is returned
@@ -48,7 +49,7 @@ EXPORTS = (
     "kh_trie_prove", "kh_verify_proofs", "kh_forest_load_nodes", "kh_forest_load_nodes_host", "kh_forest_roots",
     "kh_forest_evict", "kh_trie_open_partial", "kh_trie_open_partial_host", "kh_forest_load_partial",
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
-    "kh_trie_missing", "kh_trie_need_host",
+    "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range",
 )
 
 
@@ -192,6 +193,9 @@ def lib():
     L.kh_trie_stubs.argtypes = [vp, ctypes.POINTER(u64)]
     L.kh_trie_missing.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.kh_trie_need_host.argtypes = [vp, vp, vp, u32, u64, vp, vp]
+    L.kh_trie_range_host.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                     ctypes.POINTER(i32), vp, vp]
+    L.kh_dev_trie_range.argtypes = L.kh_trie_range_host.argtypes
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

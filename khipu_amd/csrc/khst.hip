@@ -40,6 +40,7 @@
 #include "export.h"
 #include "prove.h"
 #include "load.h"
+#include "range.h"
 
 using namespace khst;
 
@@ -6557,8 +6558,10 @@ static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
   trie_settle(h);
   kh_ctx* c = h->c;
   hipStream_t st = c->st;
+  // KH_PROVE_TRIE_KEYS: the keys are trie keys already (a range scan's), never hashed
+  const bool hash = (h->flags & KH_HASH_KEYS) && !(flags & KH_PROVE_TRIE_KEYS);
   if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
-  if (!(h->flags & KH_HASH_KEYS) && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
+  if (!hash && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
   if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
   if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
   *n_nodes = *rlp_len = *n_path = 0;
@@ -6587,7 +6590,7 @@ static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
   L1.add(scr1, scan_scratch_bytes(n + 1, 8));
   L1.add(tot, 8);
   place(h->gbuf, L1);
-  if (h->flags & KH_HASH_KEYS) {
+  if (hash) {
     if (klen <= 135)
       hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
     else
@@ -7258,7 +7261,209 @@ static int open_store_host(const uint8_t* root32, const uint8_t* enc, const uint
   })
 }
 
+// ---- range scan (range.h; the kernels are csrc/range_kernels.hip's)
+__global__ void k_range_root(AMap M, Recs R, uint32_t t, uint32_t* items);
+__global__ void k_range_count(Recs R, KeyRange g, const uint32_t* items, uint64_t n, uint64_t* cnt,
+                              unsigned long long* expand);
+__global__ void k_range_fill(AMap M, Recs R, KeyRange g, const uint32_t* items, uint64_t n, const uint64_t* pos,
+                             uint64_t cut, uint32_t* out, unsigned long long* bad);
+__global__ void k_range_lens(Recs R, const uint32_t* items, uint64_t n1, uint64_t nent, uint64_t* len,
+                             unsigned long long* res);
+__global__ void k_range_fit(Recs R, const uint32_t* items, uint64_t n1, const uint64_t* pos, uint64_t nent,
+                            const uint64_t* total, uint64_t val_cap, unsigned long long* fit, uint64_t* next);
+__global__ void k_range_write(Recs R, const uint8_t* heap, const uint32_t* items, uint64_t k, const uint64_t* pos,
+                              uint64_t bytes, uint8_t* keys32, uint64_t* voff, uint8_t* vals);
+
+// what the rounds leave in the handle's gbuf for the write: the final frontier, the scanned value
+// offsets, the entries that fit
+struct RangePage {
+  const uint32_t* items = nullptr;
+  const uint64_t* pos = nullptr;
+  uint64_t k = 0, bytes = 0;
+  uint32_t rounds = 0;
+};
+static uint32_t g_range_rounds = 0;  // rounds of the last scan (khst_range_rounds: measurements only)
+extern "C" uint32_t khst_range_rounds() { return g_range_rounds; }
+
+// The rounds of a range scan (range.h) and the fit to val_cap.  Two frontiers of max_entries + 2
+// items, one sync of a pinned word triple a round.  KH_OK with the page described in P (P.k = 0:
+// an empty answer) and *n_entries, *val_bytes, *more, next32 set; KH_ENOSPC with *val_bytes;
+// KH_ENODE with missing32.
+static int range_scan(kh_trie* h, uint32_t trie, const uint8_t* origin32, const uint8_t* limit32, uint64_t max_entries,
+                      uint64_t val_cap, RangePage& P, uint64_t* n_entries, uint64_t* val_bytes, int* more,
+                      uint8_t* next32, uint8_t* missing32) {
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  KeyRange g;
+  memset(g.o, 0, 32);
+  memset(g.l, 0xFF, 32);
+  if (origin32) memcpy(g.o, origin32, 32);
+  if (limit32) memcpy(g.l, limit32, 32);
+  const uint32_t t = h->forest ? trie : 0u;
+  // (no more entries than records: the frontiers of a call asking for 2^31 - 1 stay the trie's size)
+  const uint64_t me = std::min<uint64_t>(max_entries, std::max<uint64_t>(h->rn, 1));
+  const uint64_t F = me + 2;
+  Layout L;
+  uint32_t *fa, *fb;
+  uint64_t* cnt;
+  unsigned long long* tot;
+  char* scr;
+  L.add(fa, F + 1);
+  L.add(fb, F + 1);
+  L.add(cnt, F + 1);
+  L.add(scr, scan_scratch_bytes(F + 1, 8));
+  L.add(tot, 16);
+  place(h->gbuf, L);
+  uint64_t ni = 0;
+  uint32_t rounds = 0;
+  uint32_t *cur = fa, *nxt = fb;
+  if (h->rn && h->mcap && key_cmp(g.o, g.l) <= 0) {
+    const Recs R = recs_of(h);
+    const AMap M = map_of(h);
+    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
+    // (an empty trie, or an id the forest does not hold: the item is NONE and the first count drops it)
+    hipLaunchKernelGGL(k_range_root, dim3(1), dim3(1), 0, st, M, R, t, fa);
+    LAUNCH_CHECK();
+    for (ni = 1; ni; ++rounds) {
+      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
+      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
+      hipLaunchKernelGGL(k_range_count, GRID(ni, BS), dim3(BS), 0, st, R, g, cur, ni, cnt, tot + 1);
+      LAUNCH_CHECK();
+      scan_exclusive<uint64_t>(cnt, cnt, ni, (uint64_t*)tot, scr, st);
+      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
+      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+      const uint64_t nn = std::min(total, F);  // the cut
+      if (nn) {
+        hipLaunchKernelGGL(k_range_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, g, cur, ni,
+                           (const uint64_t*)cnt, F, nxt, tot + 2);
+        LAUNCH_CHECK();
+      }
+      std::swap(cur, nxt);
+      ni = nn;
+      if (!expand) {
+        ++rounds;
+        break;
+      }
+    }
+  }
+  P.rounds = g_range_rounds = rounds;
+  P.items = cur;
+  P.pos = cnt;
+  P.k = P.bytes = 0;
+  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
+  if (n1 == 0) {
+    *n_entries = *val_bytes = 0;
+    *more = 0;
+    return KH_OK;
+  }
+  const Recs R = recs_of(h);
+  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
+  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
+  LAUNCH_CHECK();
+  scan_exclusive<uint64_t>(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
+  hipLaunchKernelGGL(k_range_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, n1, (const uint64_t*)cnt, nent,
+                     (const uint64_t*)(tot + 12), val_cap, tot + 4, (uint64_t*)(tot + 8));
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things in range
+    const uint64_t r = (uint32_t)c->h_pinned[3];
+    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
+                          st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
+    return set_err(KH_ENODE, "the range meets a subtree the handle does not hold (missing32 names its node)");
+  }
+  const uint64_t k = c->h_pinned[4];
+  if (k == 0) {
+    *val_bytes = c->h_pinned[6];
+    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
+  }
+  P.k = k;
+  P.bytes = c->h_pinned[5];
+  *n_entries = k;
+  *val_bytes = P.bytes;
+  *more = k < n1;
+  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
+  return KH_OK;
+}
+// the page's keys, offsets and values into device buffers (P.k > 0)
+static void range_emit(kh_trie* h, const RangePage& P, uint8_t* d_keys32, uint8_t* d_vals, uint64_t* d_voff) {
+  hipLaunchKernelGGL(k_range_write, GRID(P.k + 1, BS), dim3(BS), 0, h->c->st, recs_of(h), (const uint8_t*)h->heap.p,
+                     P.items, P.k, P.pos, P.bytes, d_keys32, d_voff, d_vals);
+  LAUNCH_CHECK();
+}
+static bool range_args_ok(kh_trie* h, uint64_t max_entries, const void* keys32, const void* voff,
+                          const uint64_t* n_entries, const uint64_t* val_bytes, const int* more, const uint8_t* next32) {
+  if (!h || !keys32 || !voff || !n_entries || !val_bytes || !more || !next32) {
+    set_err(KH_EINVAL, "null handle or outputs");
+    return false;
+  }
+  if (max_entries == 0 || max_entries >= (1ULL << 31)) {
+    set_err(KH_EINVAL, "max_entries must be in [1, 2^31)");
+    return false;
+  }
+  return true;
+}
+
 extern "C" {
+
+int kh_trie_range_host(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                       uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
+                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
+  if (!range_args_ok(h, max_entries, keys32, voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    RangePage P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
+                              missing32);
+    if (rc != KH_OK) return rc;
+    voff[0] = 0;
+    if (P.k == 0) return KH_OK;
+    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
+    Layout Lo;
+    uint8_t *dk, *dv;
+    uint64_t* dvo;
+    Lo.add(dk, P.k * 32 + 64);
+    Lo.add(dvo, P.k + 1);
+    Lo.add(dv, P.bytes + 64);
+    place(c->out_emit, Lo);
+    range_emit(h, P, dk, dv, dvo);
+    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  })
+}
+
+int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                      uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
+                      uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
+  if (!range_args_ok(h, max_entries, d_keys32, d_voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    RangePage P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
+                              missing32);
+    if (rc != KH_OK) return rc;
+    if (P.k == 0) {
+      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
+    } else {
+      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
+      range_emit(h, P, d_keys32, d_vals, d_voff);
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+  })
+}
 
 int kh_trie_open_nodes(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
                        uint32_t flags, uint8_t missing32[32], kh_trie** out) {
@@ -7329,7 +7534,7 @@ int kh_trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_
                   uint32_t* path_idx, uint64_t path_cap, uint64_t* path_off, uint64_t* n_nodes, uint64_t* rlp_len,
                   uint64_t* n_path) {
   if (!h || !path_off || !n_nodes || !rlp_len || !n_path) return set_err(KH_EINVAL, "null handle or outputs");
-  if (flags & ~KH_PROVE_SHARED) return set_err(KH_EINVAL, "unknown prove flag");
+  if (flags & ~(KH_PROVE_SHARED | KH_PROVE_TRIE_KEYS)) return set_err(KH_EINVAL, "unknown prove flag");
   if (n && (!keys || !found)) return set_err(KH_EINVAL, "null buffer");
   API_TRY({
     HANDLE_LOCK(h);

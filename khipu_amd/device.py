@@ -473,6 +473,22 @@ class ResidentTrie(_Versioned):
         self.ctx._sync()
         return _prove(self.h, keys, None, shared)
 
+    def range(self, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+        """One page of the trie in key order (kh_trie_range_host; trie_range): (keys, vals, more, next)."""
+        self.ctx._sync()
+        return trie_range(self.h, origin, limit, max_entries, val_cap)
+
+    def items(self, origin=None, limit=None, chunk=1024):
+        """Generator over every (key, value) of [origin, limit] in key order, `chunk` entries a call."""
+        self.ctx._sync()
+        return _range_items(self.h, origin, limit, chunk, None)
+
+    def range_proof(self, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+        """A page with its two boundary proofs: (keys, vals, more, next, ProofTable of [origin, the
+        last returned key or limit]) -- the GetAccountRange shape."""
+        self.ctx._sync()
+        return _range_proof(self.h, origin, limit, max_entries, val_cap, None)
+
     @property
     def root_hash(self):
         return self.root
@@ -519,6 +535,70 @@ def trie_get(h, keys, trie_ids=None):
     raise RuntimeError("kh_trie_get: size negotiation failed")
 
 
+def trie_range(h, origin=None, limit=None, max_entries=1024, val_cap=1 << 20, trie=None):
+    """One page of a range scan (kh_trie_range_host): (keys, vals, more, next) -- the first entries
+    of [origin, limit] in key order, at most max_entries with values fitting val_cap; next is the
+    first key not returned when more.  Keys are trie keys (the kec256 values on a hash_keys handle).
+    KH_ENOSPC (not even the first value fits) raises KhError with the size needed in .val_bytes;
+    KH_ENODE (a partial handle: the page meets a missing subtree) raises MPTNodeMissingException
+    with the hash to fetch in .missing."""
+    n = int(max_entries)
+    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
+    ob = np.frombuffer(origin, np.uint8).copy() if origin is not None else None
+    lb = np.frombuffer(limit, np.uint8).copy() if limit is not None else None
+    if (ob is not None and ob.size != 32) or (lb is not None and lb.size != 32):
+        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
+    keys = np.zeros(32 * room, np.uint8)
+    vals = np.zeros(max(int(val_cap), 1), np.uint8)
+    voff = np.zeros(room + 1, np.uint64)
+    ne, vb, more = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    nxt = np.zeros(32, np.uint8)
+    miss = np.zeros(32, np.uint8)
+    rc = lib().kh_trie_range_host(h, 0 if trie is None else trie, ob.ctypes.data if ob is not None else None,
+                                  lb.ctypes.data if lb is not None else None, n, keys.ctypes.data, vals.ctypes.data,
+                                  int(val_cap), voff.ctypes.data, ctypes.byref(ne), ctypes.byref(vb),
+                                  ctypes.byref(more), nxt.ctypes.data, miss.ctypes.data)
+    if rc == _lib.KH_ENODE:
+        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+        e.missing = miss.tobytes()
+        raise e
+    if rc == _lib.KH_ENOSPC:
+        e = _lib.KhError(rc, lib().kh_last_error().decode())
+        e.val_bytes = int(vb.value)
+        raise e
+    check(rc)
+    k = int(ne.value)
+    return ([keys[32 * i:32 * i + 32].tobytes() for i in range(k)],
+            [vals[int(voff[i]):int(voff[i + 1])].tobytes() for i in range(k)], bool(more.value),
+            nxt.tobytes() if more.value else None)
+
+
+def _range_items(h, origin, limit, chunk, trie, val_cap=1 << 20):
+    """Every (key, value) of [origin, limit] in key order, paged by next; val_cap grows on KH_ENOSPC."""
+    while True:
+        try:
+            keys, vals, more, nxt = trie_range(h, origin, limit, chunk, val_cap, trie)
+        except _lib.KhError as e:
+            if e.code != _lib.KH_ENOSPC:
+                raise
+            val_cap = max(2 * val_cap, e.val_bytes)
+            continue
+        yield from zip(keys, vals)
+        if not more:
+            return
+        origin = nxt
+
+
+def _range_proof(h, origin, limit, max_entries, val_cap, trie):
+    """A page and the two boundary proofs a range response carries: (keys, vals, more, next, table),
+    table the shared ProofTable of [origin, the last returned key or limit] (trie keys)."""
+    keys, vals, more, nxt = trie_range(h, origin, limit, max_entries, val_cap, trie)
+    ends = [origin if origin is not None else b"\0" * 32,
+            keys[-1] if keys else (limit if limit is not None else b"\xff" * 32)]
+    _, table = trie_prove(h, ends, None if trie is None else [trie, trie], shared=True, trie_keys=True)
+    return keys, vals, more, nxt, table
+
+
 class ProofTable:
     """The node table of a kh_trie_prove call and the paths into it: nodes[j] has hash hashes[j];
     the proof of key i is nodes[path_idx[k]] for k in [path_off[i], path_off[i + 1])."""
@@ -535,9 +615,10 @@ class ProofTable:
         return [self.proof(i) for i in range(len(self.path_off) - 1)]
 
 
-def trie_prove_raw(h, keys, trie_ids=None, shared=False, caps=None):
+def trie_prove_raw(h, keys, trie_ids=None, shared=False, caps=None, trie_keys=False):
     """One kh_trie_prove call with the capacities caps = (nodes, encoding bytes, path entries):
-    (rc, (n_nodes, rlp_len, n_path), arrays), arrays = (found, hashes, rlp, off, path_idx, path_off)."""
+    (rc, (n_nodes, rlp_len, n_path), arrays), arrays = (found, hashes, rlp, off, path_idx, path_off).
+    trie_keys: KH_PROVE_TRIE_KEYS (the keys are trie keys, as a range scan returns them)."""
     keys = list(keys)
     n = len(keys)
     klen = len(keys[0]) if keys else 32
@@ -552,18 +633,19 @@ def trie_prove_raw(h, keys, trie_ids=None, shared=False, caps=None):
     po = np.zeros(n + 1, np.uint64)
     nn, nl, npth = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
     rc = lib().kh_trie_prove(h, tb.ctypes.data if tb is not None else None, kb.ctypes.data, klen, n,
-                             _lib.KH_PROVE_SHARED if shared else 0, found.ctypes.data, hs.ctypes.data, cn,
+                             (_lib.KH_PROVE_SHARED if shared else 0) | (_lib.KH_PROVE_TRIE_KEYS if trie_keys else 0),
+                             found.ctypes.data, hs.ctypes.data, cn,
                              rl.ctypes.data, cb, of.ctypes.data, pi.ctypes.data, cp, po.ctypes.data,
                              ctypes.byref(nn), ctypes.byref(nl), ctypes.byref(npth))
     return rc, (int(nn.value), int(nl.value), int(npth.value)), (found, hs, rl, of, pi, po)
 
 
-def trie_prove(h, keys, trie_ids=None, shared=False):
+def trie_prove(h, keys, trie_ids=None, shared=False, trie_keys=False):
     """Merkle proofs through kh_trie_prove (sizes negotiated): (found, ProofTable)."""
     keys = list(keys)
     caps = None
     for _ in range(3):
-        rc, sizes, (found, hs, rl, of, pi, po) = trie_prove_raw(h, keys, trie_ids, shared, caps)
+        rc, sizes, (found, hs, rl, of, pi, po) = trie_prove_raw(h, keys, trie_ids, shared, caps, trie_keys)
         if rc == _lib.KH_ENOSPC:
             caps = sizes
             continue
@@ -782,6 +864,22 @@ class ResidentForest(_Versioned):
         q = list(queries)
         self.ctx._sync()
         return _prove(self.h, [k for _, k in q], [t for t, _ in q], shared)
+
+    def range(self, trie, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+        """One page of trie `trie` in key order (kh_trie_range_host): (keys, vals, more, next); an id
+        the forest does not hold is empty."""
+        self.ctx._sync()
+        return trie_range(self.h, origin, limit, max_entries, val_cap, trie)
+
+    def items(self, trie, origin=None, limit=None, chunk=1024):
+        """Generator over every (key, value) of trie `trie` within [origin, limit], in key order."""
+        self.ctx._sync()
+        return _range_items(self.h, origin, limit, chunk, trie)
+
+    def range_proof(self, trie, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+        """ResidentTrie.range_proof for one trie of the forest."""
+        self.ctx._sync()
+        return _range_proof(self.h, origin, limit, max_entries, val_cap, trie)
 
     def last_roots(self):
         """{trie_id: root} of the last commit (kh_forest_last_roots; also after block_commit)."""
