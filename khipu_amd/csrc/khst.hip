@@ -2475,6 +2475,8 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
       LAUNCH_CHECK();
     }
   } else if (A.flags & KH_HASH_KEYS) {
+    // (hash_keys_to, written out: this first host-side use fixes where k_hash_keys<> is emitted,
+    // right after k_hash_keys_ck<> and ahead of the branch kernels, whose placement is measured)
     if (A.klen <= 135)
       hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, A.keys, A.klen, n, K32);
     else
@@ -2997,6 +2999,17 @@ static void build_stats_sums(kh_ctx* c, const unsigned long long* sums, kh_stats
   stats->t_branch_ms = ev_ms(c->ev[4], c->ev[5]);
 }
 
+// kec256 of n raw keys of klen bytes into K (KH_HASH_KEYS; one Keccak block up to 135 bytes).  It
+// stands below the build, and run_build_once keeps this dispatch written out: a kernel template is
+// emitted where its first host-side use stands, and the unit's code placement is measured.
+static void hash_keys_to(hipStream_t st, const uint8_t* keys, uint32_t klen, uint64_t n, uint64_t* K) {
+  if (klen <= 135)
+    hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, keys, klen, n, K);
+  else
+    hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, keys, klen, n, K);
+  LAUNCH_CHECK();
+}
+
 // ---------------------------------------------------------------------------
 // context management
 // ---------------------------------------------------------------------------
@@ -3060,18 +3073,25 @@ struct Staged {
   const uint64_t* voff;
   const uint32_t* seg;
 };
+// Packed host bytes data[off[0], off[n]) and their n + 1 offsets, rebased to zero, into the
+// context's in_vals / in_voff on its stream.  Nothing is checked and nothing waited for: `rel` is
+// what the second copy reads, so it lives until the caller's sync.
+static void stage_packed(kh_ctx* c, const uint8_t* data, const uint64_t* off, uint64_t n, std::vector<uint64_t>& rel) {
+  const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
+  c->in_vals.ensure(bytes + 64);
+  c->in_voff.ensure((n + 1) * 8 + 64);
+  rel.assign(n + 1, 0);
+  for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
+  if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, data + o0, bytes, hipMemcpyHostToDevice, c->st));
+  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+}
 static Staged stage_inputs(kh_ctx* c, const uint8_t* keys, uint32_t klen, const uint8_t* vals, const uint64_t* voff,
                            uint64_t n, const std::vector<uint32_t>* seg) {
-  uint64_t v0 = voff[0], vbytes = voff[n] - v0;
   c->in_keys.ensure(n * klen + 64);
-  c->in_vals.ensure(vbytes + 64);
-  c->in_voff.ensure((n + 1) * 8 + 64);
-  std::vector<uint64_t> rel(voff, voff + n + 1);
-  for (auto& x : rel) x -= v0;
+  std::vector<uint64_t> rel;
+  stage_packed(c, vals, voff, n, rel);
   hipStream_t st = c->st;
   if (n && klen) HIPCHK(hipMemcpyAsync(c->in_keys.p, keys, n * klen, hipMemcpyHostToDevice, st));
-  if (vbytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, vals + v0, vbytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
   const uint32_t* dseg = nullptr;
   if (seg) {
     c->in_seg.ensure(n * 4 + 64);
@@ -4107,8 +4127,6 @@ static JSeg journal_reserve(kh_trie* h, uint64_t nrec, uint64_t nmap) {
 // key winning; deleting an absent key is a no-op.  Fills h->tries / h->roots.  A refused
 // batch (KH_EINVAL) leaves the handle as it was, its last roots and write-back set included;
 // with a savepoint open (h->sps) every change is journaled for kh_trie_rollback.
-static void stub_missing_read(kh_trie* h, const uint32_t* d_trie, const uint64_t* d_hash,
-                              const unsigned long long* d_cnt, uint64_t cap);
 __global__ void k_stub_missing(Recs R, const uint32_t* list, uint64_t n, uint64_t cap, uint32_t* out_trie,
                                uint64_t* out_hash, unsigned long long* cnt);
 __global__ void k_stub_moved(Recs R, const uint32_t* sidx, const int8_t* pd, const uint32_t* src, const uint8_t* oldd,
@@ -4995,14 +5013,9 @@ int kh_kec256_batch(const uint8_t* data, const uint64_t* off, uint64_t n, uint8_
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(hipSetDevice(c->dev));
     if (n == 0) return KH_OK;
-    uint64_t o0 = off[0], bytes = off[n] - o0;
-    c->in_vals.ensure(bytes + 64);
-    c->in_voff.ensure((n + 1) * 8 + 64);
     c->in_keys.ensure(n * 32 + 64);
-    std::vector<uint64_t> rel(off, off + n + 1);
-    for (auto& x : rel) x -= o0;
-    if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, data + o0, bytes, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+    std::vector<uint64_t> rel;
+    stage_packed(c, data, off, n, rel);
     hipLaunchKernelGGL(k_kec_batch, GRID(n, BS), dim3(BS), 0, c->st, (const uint8_t*)c->in_vals.p,
                        (const uint64_t*)c->in_voff.p, n, (uint64_t*)c->in_keys.p);
     LAUNCH_CHECK();
@@ -5468,11 +5481,7 @@ int kh_dev_hash_keys(kh_ctx* c, const uint8_t* d_keys, uint32_t klen, uint64_t n
   API_TRY({
     HIPCHK(hipSetDevice(c->dev));
     if (n) {
-      if (klen <= 135)
-        hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, c->st, d_keys, klen, n, (uint64_t*)d_out32);
-      else
-        hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, c->st, d_keys, klen, n, (uint64_t*)d_out32);
-      LAUNCH_CHECK();
+      hash_keys_to(c->st, d_keys, klen, n, (uint64_t*)d_out32);
     }
   })
 }
@@ -5590,11 +5599,6 @@ static int verify_nodes_impl(const uint8_t* data, const uint64_t* off, uint64_t 
   std::lock_guard<std::recursive_mutex> g(c->mu);
   HIPCHK(hipSetDevice(c->dev));
   hipStream_t st = c->st;
-  const uint64_t v0 = off[0], vbytes = off[n] - v0;
-  std::vector<uint64_t> rel(off, off + n + 1);
-  for (auto& x : rel) x -= v0;
-  c->in_vals.ensure(vbytes + 64);
-  c->in_voff.ensure((n + 1) * 8 + 64);
   const uint64_t nr = nreq ? nreq : 1;
   Layout Li;
   uint64_t* dreq;
@@ -5602,8 +5606,8 @@ static int verify_nodes_impl(const uint8_t* data, const uint64_t* off, uint64_t 
   Li.add(dreq, 4 * nr + 4);
   Li.add(dkind, nr + 1);
   place(c->in_keys, Li);
-  if (vbytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, data + v0, vbytes, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+  std::vector<uint64_t> rel;
+  stage_packed(c, data, off, n, rel);
   if (nreq) {
     HIPCHK(hipMemcpyAsync(dreq, req32, 32 * nreq, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dkind, req_kind, nreq, hipMemcpyHostToDevice, st));
@@ -6266,6 +6270,25 @@ __global__ void __launch_bounds__(BS) k_get_copy(Recs R, const uint8_t* heap, co
   for (uint32_t b = 0, L = R.rvl[r]; b < L; ++b) dst[b] = src[b];
 }
 
+// what every batch of n queries must pass (hash: the keys are raw, hashed as a commit hashes them)
+static void query_check(const kh_trie* h, const uint32_t* trie, uint32_t klen, uint64_t n, bool hash) {
+  if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
+  if (!hash && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
+  if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
+  if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
+}
+// n host query keys and their trie ids (nullable) placed in the context's in_keys and copied there
+// on its stream
+static void stage_query_keys(kh_ctx* c, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
+                             uint8_t*& dk, uint32_t*& dt) {
+  Layout Lk;
+  Lk.add(dk, n * klen + 64);
+  Lk.add(dt, n, trie != nullptr);
+  place(c->in_keys, Lk);
+  if (n) HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, c->st));
+  if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, c->st));
+}
+
 // n queries (device buffers): the keys (the trie's key encoder applied, as in a commit),
 // their trie ids (forests; NULL = trie 0), then the found flags, the packed values and
 // their offsets.  Returns KH_ENOSPC (writing only *val_bytes) when val_cap is too small.
@@ -6273,10 +6296,7 @@ static int trie_get(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, u
                     uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff, uint8_t* d_found, uint64_t* val_bytes) {
   kh_ctx* c = h->c;
   hipStream_t st = c->st;
-  if (h->forest && n && !d_trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
-  if (!(h->flags & KH_HASH_KEYS) && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
-  if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
-  if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
+  query_check(h, d_trie, klen, n, h->flags & KH_HASH_KEYS);
   Layout L;
   uint64_t *K, *len, *tot;
   uint32_t* rec;
@@ -6289,11 +6309,7 @@ static int trie_get(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, u
   place(h->gbuf, L);
   if (n) {
     if (h->flags & KH_HASH_KEYS) {
-      if (klen <= 135)
-        hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, d_keys, klen, n, K);
-      else
-        hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, d_keys, klen, n, K);
-      LAUNCH_CHECK();
+      hash_keys_to(st, d_keys, klen, n, K);
     } else {
       HIPCHK(hipMemcpyAsync(K, d_keys, n * 32, hipMemcpyDeviceToDevice, st));
     }
@@ -6347,18 +6363,14 @@ int kh_trie_get_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
     // staging: keys and trie ids in, found flags, offsets and values out
-    Layout Lk, Lo;
+    Layout Lo;
     uint8_t *dk, *df, *dv;
     uint32_t* dt;
-    Lk.add(dk, n * klen + 64);
-    Lk.add(dt, n, trie != nullptr);
-    place(c->in_keys, Lk);
     c->in_voff.ensure((n + 1) * 8 + 64);
     Lo.add(df, n + 64);
     Lo.add(dv, val_cap + 64);
     place(c->out_emit, Lo);
-    if (n) HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
-    if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, st));
+    stage_query_keys(c, trie, keys, klen, n, dk, dt);
     const int rc = trie_get(h, dt, dk, klen, n, dv, val_cap, (uint64_t*)c->in_voff.p, df, val_bytes);
     if (rc != KH_OK) return rc;
     HIPCHK(hipMemcpyAsync(voff, c->in_voff.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -6560,10 +6572,7 @@ static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
   hipStream_t st = c->st;
   // KH_PROVE_TRIE_KEYS: the keys are trie keys already (a range scan's), never hashed
   const bool hash = (h->flags & KH_HASH_KEYS) && !(flags & KH_PROVE_TRIE_KEYS);
-  if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
-  if (!hash && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
-  if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
-  if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
+  query_check(h, trie, klen, n, hash);
   *n_nodes = *rlp_len = *n_path = 0;
   if (n == 0) {
     path_off[0] = 0;
@@ -6572,14 +6581,9 @@ static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
   }
   const bool shared = (flags & KH_PROVE_SHARED) != 0;
   // the keys and trie ids staged, the keys hashed as a commit hashes them
-  Layout Lk;
   uint8_t* dk;
   uint32_t* dt;
-  Lk.add(dk, n * klen + 64);
-  Lk.add(dt, n, trie != nullptr);
-  place(c->in_keys, Lk);
-  HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
-  if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, st));
+  stage_query_keys(c, trie, keys, klen, n, dk, dt);
   Layout L1;
   uint64_t *K, *pos, *tot;
   uint8_t* fnd;
@@ -6591,11 +6595,7 @@ static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
   L1.add(tot, 8);
   place(h->gbuf, L1);
   if (hash) {
-    if (klen <= 135)
-      hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-    else
-      hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-    LAUNCH_CHECK();
+    hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
   } else {
     HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
   }
@@ -6769,11 +6769,7 @@ static int verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t*
   Lw.add(tot, 8);
   place(c->ws1, Lw);
   if (flags & KH_HASH_KEYS) {
-    if (klen <= 135)
-      hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-    else
-      hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-    LAUNCH_CHECK();
+    hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
   } else {
     HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
   }
@@ -7205,13 +7201,8 @@ static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint6
   for (uint64_t i = 0; i < n; ++i)
     if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
   if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
-  const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
-  c->in_vals.ensure(bytes + 64);
-  c->in_voff.ensure((n + 1) * 8 + 64);
-  std::vector<uint64_t> rel(n + 1, 0);
-  for (uint64_t i = 0; i <= n && n; ++i) rel[i] = off[i] - o0;
-  if (bytes) HIPCHK(hipMemcpyAsync(c->in_vals.p, enc + o0, bytes, hipMemcpyHostToDevice, c->st));
-  HIPCHK(hipMemcpyAsync(c->in_voff.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->st));
+  std::vector<uint64_t> rel;
+  stage_packed(c, enc, off, n, rel);
   HIPCHK(hipStreamSynchronize(c->st));
   return KH_OK;
 }
@@ -7258,6 +7249,35 @@ static int open_store_host(const uint8_t* root32, const uint8_t* enc, const uint
     if (rc != KH_OK) return rc;
     *out = open_store(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags, missing32, mode,
                       true);
+  })
+}
+
+// The body of kh_forest_load_nodes, kh_forest_load_partial and kh_trie_fill_nodes (a fill: no trie
+// list, no missing list, and any handle) and of their _host forms, whose store is staged first
+// (stage_store makes its own checks of it).
+static int load_entry(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* enc,
+                      const uint64_t* off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
+                      uint64_t* n_missing, kh_stats* stats, LoadMode mode, uint64_t* n_decoded, bool host) {
+  if (n_missing) *n_missing = 0;
+  if (n_decoded) *n_decoded = 0;
+  if (mode == LOAD_FILL) {
+    if (!h) return set_err(KH_EINVAL, "null handle");
+  } else if (!h || !h->forest) {
+    return set_err(KH_EINVAL, "null handle or not a forest");
+  }
+  if ((k && (!tries || !roots32)) || (!host && n && (!enc || !off)) || (miss_cap && (!miss_idx || !miss32)))
+    return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    if (host) {
+      const int rc = stage_store(c, enc, off, n);
+      if (rc != KH_OK) return rc;
+      enc = (const uint8_t*)c->in_vals.p;
+      off = (const uint64_t*)c->in_voff.p;
+    }
+    forest_load(h, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, mode, n_decoded);
   })
 }
 
@@ -7479,32 +7499,15 @@ int kh_trie_open_nodes_host(const uint8_t root32[32], const uint8_t* enc, const 
 int kh_forest_load_nodes(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
                          const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
                          uint64_t* n_missing, kh_stats* stats) {
-  if (n_missing) *n_missing = 0;
-  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if ((k && (!tries || !roots32)) || (n && (!d_enc || !d_off)) || (miss_cap && (!miss_idx || !miss32)))
-    return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(f);
-    HIPCHK(hipSetDevice(f->c->dev));
-    forest_load(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats);
-  })
+  return load_entry(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_FULL,
+                    nullptr, false);
 }
 
 int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
                               const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32,
                               uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
-  if (n_missing) *n_missing = 0;
-  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if ((k && (!tries || !roots32)) || (miss_cap && (!miss_idx || !miss32))) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(f);
-    kh_ctx* c = f->c;
-    HIPCHK(hipSetDevice(c->dev));
-    const int rc = stage_store(c, enc, off, n);
-    if (rc != KH_OK) return rc;
-    forest_load(f, tries, roots32, k, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, miss_idx, miss32,
-                miss_cap, n_missing, stats);
-  })
+  return load_entry(f, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_FULL,
+                    nullptr, true);
 }
 
 int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries) {
@@ -7616,59 +7619,27 @@ int kh_trie_open_partial_host(const uint8_t root32[32], const uint8_t* enc, cons
 int kh_forest_load_partial(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
                            const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
                            uint64_t* n_missing, kh_stats* stats) {
-  if (n_missing) *n_missing = 0;
-  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if ((k && (!tries || !roots32)) || (n && (!d_enc || !d_off)) || (miss_cap && (!miss_idx || !miss32)))
-    return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(f);
-    HIPCHK(hipSetDevice(f->c->dev));
-    forest_load(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL);
-  })
+  return load_entry(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL,
+                    nullptr, false);
 }
 
 int kh_forest_load_partial_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
                                 const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx,
                                 uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
-  if (n_missing) *n_missing = 0;
-  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if ((k && (!tries || !roots32)) || (miss_cap && (!miss_idx || !miss32))) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(f);
-    kh_ctx* c = f->c;
-    HIPCHK(hipSetDevice(c->dev));
-    const int rc = stage_store(c, enc, off, n);
-    if (rc != KH_OK) return rc;
-    forest_load(f, tries, roots32, k, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, miss_idx, miss32,
-                miss_cap, n_missing, stats, LOAD_PARTIAL);
-  })
+  return load_entry(f, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL,
+                    nullptr, true);
 }
 
 int kh_trie_fill_nodes(kh_trie* h, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n, uint64_t* n_decoded,
                        kh_stats* stats) {
-  if (n_decoded) *n_decoded = 0;
-  if (!h) return set_err(KH_EINVAL, "null handle");
-  if (n && (!d_enc || !d_off)) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(h);
-    HIPCHK(hipSetDevice(h->c->dev));
-    forest_load(h, nullptr, nullptr, 0, d_enc, d_off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded);
-  })
+  return load_entry(h, nullptr, nullptr, 0, d_enc, d_off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded,
+                    false);
 }
 
 int kh_trie_fill_nodes_host(kh_trie* h, const uint8_t* enc, const uint64_t* off, uint64_t n, uint64_t* n_decoded,
                             kh_stats* stats) {
-  if (n_decoded) *n_decoded = 0;
-  if (!h) return set_err(KH_EINVAL, "null handle");
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    const int rc = stage_store(c, enc, off, n);
-    if (rc != KH_OK) return rc;
-    forest_load(h, nullptr, nullptr, 0, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, nullptr,
-                nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded);
-  })
+  return load_entry(h, nullptr, nullptr, 0, enc, off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded,
+                    true);
 }
 
 int kh_trie_stubs(const kh_trie* h, uint64_t* n) {
@@ -7701,10 +7672,7 @@ int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
     kh_ctx* c = h->c;
     HIPCHK(hipSetDevice(c->dev));
     hipStream_t st = c->st;
-    if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
-    if (!(h->flags & KH_HASH_KEYS) && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
-    if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
-    if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "too many queries"};
+    query_check(h, trie, klen, n, h->flags & KH_HASH_KEYS);
     if (n == 0) return KH_OK;
     trie_settle(h);
     if (!(h->nstubs && h->rn && h->mcap)) {  // no stub to reach
@@ -7712,25 +7680,17 @@ int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
       memset(need32, 0, n * 32);
       return KH_OK;
     }
-    Layout Lk, L;
+    Layout L;
     uint8_t *dk, *df;
     uint32_t* dt;
     uint64_t *K, *dh;
-    Lk.add(dk, n * klen + 64);
-    Lk.add(dt, n, trie != nullptr);
-    place(c->in_keys, Lk);
     L.add(K, n * 4 + 8);
     L.add(dh, n * 4);
     L.add(df, n + 64);
     place(h->gbuf, L);
-    HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
-    if (dt) HIPCHK(hipMemcpyAsync(dt, trie, n * 4, hipMemcpyHostToDevice, st));
+    stage_query_keys(c, trie, keys, klen, n, dk, dt);
     if (h->flags & KH_HASH_KEYS) {
-      if (klen <= 135)
-        hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-      else
-        hipLaunchKernelGGL(k_hash_keys<false>, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)dk, klen, n, K);
-      LAUNCH_CHECK();
+      hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
     } else {
       HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
     }

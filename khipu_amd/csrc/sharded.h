@@ -171,11 +171,7 @@ static void sharded_root(const int* devices, int ngpus, const uint8_t* keys, uin
     const uint8_t* K = in.keys;
     if (flags & KH_HASH_KEYS) {
       s.k32.ensure(s.n * 32 + 64, c->dev);
-      if (klen <= 135)
-        hipLaunchKernelGGL(k_hash_keys<true>, GRID(s.n, BS), dim3(BS), 0, c->st, in.keys, klen, s.n, (uint64_t*)s.k32.p);
-      else
-        hipLaunchKernelGGL(k_hash_keys<false>, GRID(s.n, BS), dim3(BS), 0, c->st, in.keys, klen, s.n, (uint64_t*)s.k32.p);
-      LAUNCH_CHECK();
+      hash_keys_to(c->st, in.keys, klen, s.n, (uint64_t*)s.k32.p);
       K = (const uint8_t*)s.k32.p;
     }
     const uint64_t vb = voff[s.lo + s.n] - voff[s.lo];

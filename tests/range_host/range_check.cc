@@ -9,8 +9,8 @@
 //   R originhex limithex max_entries val_cap cut_slack
 //                         a range; the frontier is cut at max_entries + cut_slack items (2 is the
 //                         library's; 1 shows that the inputs can see the cut)
-// The program builds the records of the trie bottom-up (the builder of tests/prove_host, with
-// export.h's own bodies), prints
+// The program builds the records of the trie bottom-up (the builder of
+// tests/host_common/replay.h, with export.h's own bodies), prints
 //   T roothex
 // and replays every range through range.h's bodies as range_kernels.hip runs them: count, exclusive
 // scan, 16 lanes an item in the fill, into a next frontier of exactly the items it takes (never
@@ -19,144 +19,9 @@
 //   A page k more nexthex|- rounds key_1 val_1 .. key_k val_k
 //   A nospc size
 //   A missing hashhex
-#include <algorithm>
-#include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
+#include "../host_common/replay.h"
 
 #include "../../khipu_amd/csrc/range.h"
-
-using namespace khst;
-typedef std::array<uint8_t, 32> Key;
-typedef std::vector<uint8_t> Bytes;
-
-static Bytes unhex(const std::string& s) {
-  Bytes o;
-  if (s == "-") return o;
-  for (size_t i = 0; i + 1 < s.size(); i += 2) o.push_back((uint8_t)strtoul(s.substr(i, 2).c_str(), nullptr, 16));
-  return o;
-}
-static void put_hex(const uint8_t* p, size_t n) {
-  if (!n) printf("-");
-  for (size_t i = 0; i < n; ++i) printf("%02x", p[i]);
-}
-static uint32_t nib(const Key& k, uint32_t i) { return (i & 1) ? (k[i >> 1] & 0xF) : (k[i >> 1] >> 4); }
-static void kec(const Bytes& e, uint64_t out[4]) {
-  std::vector<uint64_t> w((e.size() + 15) / 8, 0);
-  memcpy(w.data(), e.data(), e.size());
-  kec256_msg<false>((const uint8_t*)w.data(), (uint32_t)e.size(), out);
-}
-
-struct Host {
-  uint8_t* recs = nullptr;
-  uint8_t* slots = nullptr;
-  Bytes heap;
-  uint64_t rn = 0, cap = 0;
-  Recs R;
-  AMap M;
-  std::vector<Key> keys;
-  std::vector<Bytes> vals;
-  std::vector<uint8_t> vb;
-
-  void init(uint64_t nkeys) {
-    cap = 2 * nkeys + 4;
-    recs = (uint8_t*)aligned_alloc(128, cap * REC_BYTES);
-    memset(recs, 0, cap * REC_BYTES);
-    uint64_t mc = 16;
-    while (mc < 4 * cap) mc <<= 1;
-    slots = (uint8_t*)aligned_alloc(128, mc * 16);
-    memset(slots, 0, mc * 16);
-    R = recs_at(recs);
-    M = AMap{{slots}, {slots}, mc - 1};
-  }
-  void anchor(uint32_t r) {
-    const uint64_t tag = anchor_tag(R.rt[r], R.rd[r], R.key(r));
-    uint64_t s = tag & M.mask;
-    while (M.tag[s]) s = (s + 1) & M.mask;
-    M.tag[s] = tag;
-    M.rec[s] = r;
-  }
-  Bytes encode(uint64_t r, uint32_t sel) {
-    uint32_t child[EXP_LANES], il[EXP_LANES], pre[EXP_LANES], S = 0, len[2];
-    const bool need = exp_needs_children(R, r, sel);
-    for (uint32_t c = 0; c < EXP_LANES; ++c) {
-      child[c] = need ? exp_child(R, M, r, c) : NONE;
-      il[c] = need ? exp_item_len(R, child[c]) : 0;
-      pre[c] = S;
-      S += il[c];
-    }
-    uint32_t cnt = 0, bytes = 0;
-    exp_sizes(R, heap.data(), r, sel, S, &cnt, &bytes);
-    Bytes out(bytes);
-    for (uint32_t lane = 0; lane < EXP_LANES; ++lane)
-      exp_write(R, heap.data(), r, sel, lane, child[lane], pre[lane], S, out.data(), len);
-    if (len[0] + len[1] != bytes) exit(3);
-    return out;
-  }
-  void capped(const Bytes& e, uint64_t ref[4], uint8_t* rl) {
-    if (e.size() >= 32) {
-      kec(e, ref);
-      *rl = 32;
-    } else {
-      words_of(e.data(), (uint32_t)e.size(), ref);
-      *rl = (uint8_t)e.size();
-    }
-  }
-  // records of the subtrie of sorted keys [lo, hi) hanging at depth d
-  uint32_t build(size_t lo, size_t hi, uint32_t d) {
-    uint32_t db = EL_LEAF, mask = 0;
-    if (hi - lo > 1) {
-      db = d;
-      while (nib(keys[lo], db) == nib(keys[hi - 1], db)) ++db;
-      for (size_t i = lo; i < hi;) {
-        const uint32_t c = nib(keys[i], db);
-        size_t j = i;
-        while (j < hi && nib(keys[j], db) == c) ++j;
-        build(i, j, db + 1);
-        mask |= 1u << c;
-        i = j;
-      }
-    } else if (vb[lo]) {
-      if (d != 64) exit(5);  // (a value-only branch hangs under a depth-63 branch)
-      db = VB_DEPTH;
-    }
-    const uint32_t r = (uint32_t)rn++;
-    if (rn > cap) exit(4);
-    memcpy(R.key(r), keys[lo].data(), 32);
-    R.rt[r] = 0;
-    R.rd[r] = (uint8_t)d;
-    R.rdb[r] = (uint8_t)db;
-    R.rmask[r] = (uint16_t)mask;
-    R.rlive[r] = REC_LIVE;
-    if (db == EL_LEAF || db == VB_DEPTH) {
-      R.rvo[r] = heap.size();
-      R.rvl[r] = (uint32_t)vals[lo].size();
-      heap.insert(heap.end(), vals[lo].begin(), vals[lo].end());
-    }
-    uint64_t ref[4];
-    uint8_t rl;
-    if (exp_has_lower(d, db)) {
-      capped(encode(r, EXP_LOWER), ref, &rl);
-      for (int q = 0; q < 4; ++q) R.rbref[4ull * r + q] = ref[q];
-      R.rbrl[r] = rl;
-    }
-    capped(encode(r, EXP_UPPER), ref, &rl);
-    for (int q = 0; q < 4; ++q) R.rref[4ull * r + q] = ref[q];
-    R.rrl[r] = rl;
-    if (!exp_has_lower(d, db)) {
-      for (int q = 0; q < 4; ++q) R.rbref[4ull * r + q] = ref[q];
-      R.rbrl[r] = rl;
-    }
-    anchor(r);
-    return r;
-  }
-};
 
 // one range, as kh_trie_range_host runs it (khst.hip range_scan / range_emit)
 static void range(const Host& H, const Key& origin, const Key& limit, uint64_t max_entries, uint64_t val_cap,
@@ -264,11 +129,6 @@ int main(int argc, char** argv) {
   if (argc < 2) return 2;
   std::ifstream f(argv[1]);
   if (!f) return 2;
-  struct Put {
-    Key k;
-    Bytes v;
-    bool vb;
-  };
   std::vector<Put> in;
   std::vector<std::string> rlines;
   std::string line;
@@ -289,23 +149,9 @@ int main(int argc, char** argv) {
       rlines.push_back(line);
     }
   }
-  std::stable_sort(in.begin(), in.end(), [](const Put& x, const Put& y) { return x.k < y.k; });
-  Host H;
-  for (size_t i = 0; i < in.size(); ++i) {
-    if (i + 1 < in.size() && in[i + 1].k == in[i].k) continue;
-    H.keys.push_back(in[i].k);
-    H.vals.push_back(in[i].v);
-    H.vb.push_back(in[i].vb);
-  }
-  H.init(H.keys.size());
+  Builder H(in);
   uint8_t root[32];
-  memcpy(root, empty_root_hash(), 32);
-  if (!H.keys.empty()) {
-    const uint32_t r = H.build(0, H.keys.size(), 0);
-    uint64_t h[4];
-    kec(H.encode(r, EXP_UPPER), h);
-    memcpy(root, h, 32);
-  }
+  H.root_hash(root);
   printf("T ");
   put_hex(root, 32);
   printf("\n");
@@ -321,7 +167,5 @@ int main(int argc, char** argv) {
     memcpy(l.data(), lb.data(), 32);
     range(H, o, l, mx, cap, slack);
   }
-  free(H.recs);
-  free(H.slots);
   return 0;
 }

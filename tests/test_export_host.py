@@ -3,29 +3,15 @@ AddressSanitizer and UBSan.  tests/export_host/export_check.cc (a stand-alone pr
 trie's records bottom-up with the encoder itself, runs the sizes and write bodies over them into
 buffers of exactly the scanned size, and prints the node set; it must equal the oracle's
 reachable() -- every node with an encoding >= 32 B, plus the root."""
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
-from tests import export_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "export_host", "export_check.cc")
+from tests import export_cases, hostprog
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp_path_factory.mktemp("export_host") / "export_check"
-    r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+prog = hostprog.prog_fixture("export")
 
 
 def _run(prog, tmp_path, keys, vals, *args):

@@ -5,10 +5,11 @@ compared with a plain nibble-list reference for every depth 0..64: the cases at 
 program runs twice: built plain, and built with AddressSanitizer and UBSan."""
 import os
 import random
-import shutil
 import subprocess
 
 import pytest
+
+from tests import hostprog
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "keyprims_host", "keyprims_check.cc")
@@ -70,14 +71,9 @@ def _inputs():
 
 
 def _build(tmp, sanitize):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp / ("keyprims_check_san" if sanitize else "keyprims_check")
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    r = subprocess.run([cxx, "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas"] + flags
-                       + ["-o", str(exe), SRC], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+    if sanitize:
+        return hostprog.compile_prog(SRC, tmp / "keyprims_check_san")
+    return hostprog.compile_prog(SRC, tmp / "keyprims_check", ["-O2", "-std=c++17"])
 
 
 @pytest.fixture(scope="module", params=[False, True], ids=["plain", "sanitized"])

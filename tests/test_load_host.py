@@ -4,32 +4,23 @@ UBSan.  tests/load_host/load_check.cc (a stand-alone program) takes a node store
 sizes, builds an anchor map over the records and re-encodes every record through export.h.  Each
 trie's node set must equal the oracle's reachable() bit for bit; missing nodes must be listed
 exactly; malformed nodes must give their error code and leave nothing behind."""
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
 from tests import cases as C
-from tests import export_cases, proof_cases
+from tests import export_cases, hostprog, proof_cases
+from tests.hostprog import rlp_list as _lst
+from tests.hostprog import rlp_str as _s
+from tests.hostprog import trie as _trie
+from tests.hostprog import vb_trie as _vb_trie
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "load_host", "load_check.cc")
 EMPTY = bytes.fromhex("56e81f171bcc55a6ff8345e692c0f86e5b48e01b996cadc001622fb5e363b421")
 OK, MISSING, BAD, VALUE = 0, 1, 2, 3  # forest.h OPEN_*
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp_path_factory.mktemp("load_host") / "load_check"
-    r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+prog = hostprog.prog_fixture("load")
 
 
 def _run(prog, tmp_path, store, tries):
@@ -51,26 +42,6 @@ def _run(prog, tmp_path, store, tries):
             per[h] = bytes.fromhex(x[3])
     det = [x for x in out if x[0] == "D"]
     return s, miss, nodes, det[0][1] == "1"
-
-
-def _trie(oracle, keys, vals):
-    o = oracle.Trie()
-    for k, v in zip(keys, vals):
-        o.put(k, v)
-    return o
-
-
-def _vb_trie(oracle):
-    """khipu's value-only branch: a re-put of a key whose leaf hangs under a depth-63 branch."""
-    ks, vs, blocks, _ = proof_cases.vb_case(False)
-    o = _trie(oracle, ks, vs)
-    for ups, dels in blocks[:1]:
-        for k, v in ups:
-            o.put(k, v)
-        for k in dels:
-            o.remove(k)
-    live = {k: o.get(k) for k in ks}
-    return o, sum(1 for v in live.values() if v is not None)
 
 
 def _cases(oracle):
@@ -148,16 +119,6 @@ def test_host_missing_nodes_are_listed_exactly(prog, tmp_path, oracle):
     s, miss, nodes, _ = _run(prog, tmp_path, [e for h, e in full.items() if h != grand], tries)
     assert s["code"] == MISSING and s["rounds"] == 2 and s["records"] == 0 and not nodes
     assert miss == [(1, grand)]
-
-
-def _s(b):
-    return bytes([0x80 + len(b)]) + b if len(b) != 1 or b[0] >= 0x80 else b
-
-
-def _lst(items):
-    p = b"".join(items)
-    return (bytes([0xC0 + len(p)]) if len(p) < 56 else bytes([0xF8, len(p)]) if len(p) < 256
-            else bytes([0xF9, len(p) >> 8, len(p) & 255])) + p
 
 
 def malformed_roots():

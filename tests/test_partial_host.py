@@ -4,33 +4,24 @@ program) replays the rounds into arrays of exactly the scanned sizes, builds an 
 records, re-encodes every non-stub record through export.h and runs the get, need and prove walks.
 Every expectation is the oracle's: reachable() minus the subtrees withheld, the child items of the
 nodes that are there, and tests/proof_ref.expected_proof."""
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
 from tests import cases as C
-from tests import export_cases, proof_cases, proof_ref
+from tests import export_cases, hostprog, proof_cases, proof_ref
+from tests.hostprog import rlp_list as _lst
+from tests.hostprog import rlp_str as _s
+from tests.hostprog import trie as _trie
+from tests.hostprog import vb_trie as _vb_trie
 from tests.partial_cases import hash_children as _hash_children
 from tests.partial_cases import subtree as _subtree
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "partial_host", "partial_check.cc")
 OK, MISSING, BAD, VALUE = 0, 1, 2, 3  # forest.h OPEN_*
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp_path_factory.mktemp("partial_host") / "partial_check"
-    r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+prog = hostprog.prog_fixture("partial")
 
 
 class Out:
@@ -73,13 +64,6 @@ def _run(prog, tmp_path, store, tries, fill=None, queries=()):
     det = [x for x in out if x[0] == "D"][0][1] == "1"
     after = Out(out, "F") if any(x[0] == "FS" for x in out) else None
     return Out(out, ""), after, miss, g, det
-
-
-def _trie(oracle, keys, vals):
-    o = oracle.Trie()
-    for k, v in zip(keys, vals):
-        o.put(k, v)
-    return o
 
 
 def _random_tries(oracle):
@@ -185,17 +169,6 @@ def test_host_extension_whose_branch_is_missing(prog, tmp_path, oracle):
     assert b.s["code"] == OK and b.s["stubs"] == 0 and b.nodes == {0: enc} and b.s["keys"] == len(ek)
 
 
-def _vb_trie(oracle):
-    ks, vs, blocks, _ = proof_cases.vb_case(False)
-    o = _trie(oracle, ks, vs)
-    for ups, dels in blocks[:1]:
-        for k, v in ups:
-            o.put(k, v)
-        for k in dels:
-            o.remove(k)
-    return o, sum(1 for k in ks if o.get(k) is not None)
-
-
 def test_host_embedded_nodes_are_never_stubs(prog, tmp_path, oracle):
     keys, vals = export_cases.embedded_case()
     o = _trie(oracle, keys, vals)
@@ -213,16 +186,6 @@ def test_host_value_only_branch_leaves_no_stub(prog, tmp_path, oracle):
     a, _, _, _, det = _run(prog, tmp_path, list(want.values()), [(3, o.root_hash())])
     assert a.s["code"] == OK and det and a.s["keys"] == nkeys and a.s["stubs"] == 0
     assert a.nodes == {3: want}
-
-
-def _s(b):
-    return bytes([0x80 + len(b)]) + b if len(b) != 1 or b[0] >= 0x80 else b
-
-
-def _lst(items):
-    p = b"".join(items)
-    return (bytes([0xC0 + len(p)]) if len(p) < 56 else bytes([0xF8, len(p)]) if len(p) < 256
-            else bytes([0xF9, len(p) >> 8, len(p) & 255])) + p
 
 
 def test_host_fill_with_a_malformed_node_two_rounds_down(prog, tmp_path, oracle):

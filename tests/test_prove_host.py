@@ -4,39 +4,19 @@ bottom-up, runs the count walk and the fill walk into arrays of exactly the coun
 every hit through export.h and feeds proofs -- its own, and mutated and malformed ones from its
 input file -- to the verify walk.  The proofs must equal tests/proof_ref.expected_proof bit for
 bit and the statuses tests/proof_ref.check_proof."""
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
 from tests import cases as C
-from tests import export_cases, proof_cases
+from tests import export_cases, hostprog, proof_cases
 from tests import proof_ref as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "prove_host", "prove_check.cc")
-
-
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp_path_factory.mktemp("prove_host") / "prove_check"
-    r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
+from tests.hostprog import hexs as _hex
+from tests.hostprog import unhexs as _unhex
 
 
-def _hex(b):
-    return b.hex() or "-"
-
-
-def _unhex(s):
-    return b"" if s == "-" else bytes.fromhex(s)
+prog = hostprog.prog_fixture("prove")
 
 
 def _run(prog, tmp_path, puts=(), queries=(), verifies=()):

@@ -4,41 +4,22 @@ and runs the rounds as range_kernels.hip does -- count, scan, a 16-lane fill int
 max_entries + 2 items, lengths, fit, write into outputs of exactly the scanned sizes.  Every answer
 must equal tests/range_ref.expected_range over the oracle's nodes; and the same inputs with the
 cut at max_entries + 1 must disagree somewhere, so the inputs can see the cut."""
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
 from tests import cases as C
-from tests import export_cases, proof_cases
+from tests import export_cases, hostprog, proof_cases
 from tests import range_cases as RC
 from tests import range_ref as RR
+from tests.hostprog import hexs as _hex
+from tests.hostprog import unhexs as _unhex
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "range_host", "range_check.cc")
 NAMES = ["one_key", "random300", "embedded", "extension", "value_only_branch", "dense"]
 
 
-@pytest.fixture(scope="module")
-def prog(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    assert cxx, "no C++ compiler"
-    exe = tmp_path_factory.mktemp("range_host") / "range_check"
-    r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", str(exe), SRC],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(exe)
-
-
-def _hex(b):
-    return b.hex() or "-"
-
-
-def _unhex(s):
-    return b"" if s == "-" else bytes.fromhex(s)
+prog = hostprog.prog_fixture("range")
 
 
 def _run(prog, tmp_path, puts, ranges, slack=2):
