@@ -41,6 +41,10 @@
  *   kh_trie_prove           the nodes MerklePatriciaTrie.get visits (MerklePatriciaTrie.scala:90-147)
  *                           for a batch of keys: an eth_getProof answer, or a block's witness
  *   kh_verify_proofs        that walk re-done from a root over the listed nodes alone
+ *   kh_verify_ranges        range responses (a page of kh_trie_range_host with its two boundary proofs,
+ *                           or whole small tries) checked against their roots without a handle: nothing
+ *                           left out between origin and the last key (no reference counterpart: khipu
+ *                           syncs node by node; the contract is snap's, geth's VerifyRangeProof)
  *
  * Semantics shared by every trie entry point:
  *   - input i is a put(key_i, value_i); later inputs overwrite earlier ones with the
@@ -665,6 +669,67 @@ int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], con
                       uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32],
                       uint8_t missing32[32]);
+
+/* ---- range verification: range responses checked against a root, without a handle ----
+ * The receiving half of kh_trie_range_host + kh_trie_prove(KH_PROVE_TRIE_KEYS) (snap's ranges,
+ * geth's VerifyRangeProof), nr ranges a call over ONE node set.  Range s: root roots32[32s..),
+ * origin origins32[32s..) (origins32 NULL: all zero), entries ent_off[s] .. ent_off[s+1] of keys32 /
+ * vals / voff (entry i: key keys32[32i..), value vals[voff[i]..voff[i+1])).  Keys are 32-byte TRIE
+ * keys and are never hashed here (on a KH_HASH_KEYS handle: the kec256 values a range scan
+ * returns).  The node set has the layout of kh_trie_open_nodes: n_nodes encodings enc[off[j]..
+ * off[j+1]), content addressed (hashed here); duplicates and strangers are fine.  proved[s] = 0:
+ * the entries claim to be the whole trie, no node is read; 1: the boundary proof of origin and of
+ * the last key (of origin alone without entries) is taken from the node set.  There is no limit:
+ * a responder may stop anywhere, the caller compares the last key with its limit.
+ * Per range, with o = origin, k_1..k_m the entries and hi = k_m (o when m = 0):
+ *   1. keys strictly ascending, k_1 >= o, every value >= 1 byte -- else BAD_ORDER, decided before
+ *      any node is read.
+ *   2. proved = 0: OK iff the root of the trie of the entries is the root (EMPTY_TRIE_HASH for
+ *      m = 0), else BAD_ROOT; more = 0.
+ *   3. proved = 1: the walk goes down from the root along o's path and hi's path only.  A child of
+ *      a branch whose prefix is below o's is kept as an opaque subtree (its reference: a 32-byte
+ *      hash or an embedded list < 32 B), above hi's prefix likewise and more = 1, on a path it is
+ *      entered (a hash absent from the node set: MISSING), strictly between it is dropped.  A
+ *      leaf or extension is HexPrefix-decoded to its full prefix q: an extension that is a prefix
+ *      of o or of hi is entered; else q below o: kept as the node itself, above hi: kept and
+ *      more = 1, within: dropped (so a leaf in [o, hi] must be among the entries).  A value-only
+ *      branch at nibble 64 counts as a leaf.  Nodes must be well formed by kh_verify_proofs'
+ *      rules (and a leaf's path must end at nibble 64), else BAD_NODE.  Each path stops at its
+ *      first problem; BAD_NODE on either path wins over MISSING; missing32 is the hash on o's
+ *      path if that path has one, else hi's.  Nodes never met are ignored.
+ *   4. m = 0 and more = 1: INCOMPLETE.
+ *   5. the canonical trie over the entries (leaves) and the kept subtrees at their prefixes is
+ *      hashed: OK iff its root is the given one, else BAD_ROOT -- also when a kept subtree would
+ *      have to move (its parent branch would have it as the only child, an entry would run under
+ *      its prefix), which only a response that omits or invents entries produces.
+ * Limit: a range whose inside holds one of khipu's value-only branches (a re-put key under a
+ * depth-63 branch) cannot be expressed by entries and reports BAD_ROOT.
+ * An honest response cut at its end stays valid while the new last key's path is in the node
+ * set: the cut entries become subtrees kept on the right and more = 1.
+ * Outputs: status[s]; more[s] = 1 iff the trie holds a key above hi (meaningful for OK and
+ * INCOMPLETE); missing32 (nullable) [32s..) for MISSING, zero otherwise.
+ * KH_EINVAL, nothing written: a null array (vals may be NULL only when no entry has a byte);
+ * ent_off, voff or off not non-decreasing (checked by kh_verify_ranges; a precondition of the
+ * device form); nr, the entry total or n_nodes >= 2^31.
+ * kh_dev_verify_ranges: every input array in HBM (ctx NULL: the context the host forms use), on
+ * the context's stream.  d_roots32, d_origins32 and d_keys32 are read as 64-bit words: they and the
+ * offset arrays must be 8-byte aligned, and d_ent_off[0] = 0 (KH_EINVAL otherwise); every value is
+ * shorter than 2^32 bytes (a precondition).  status, more and missing32 are host arrays, valid on
+ * return. */
+#define KH_RANGE_OK 0          /* the entries are exactly the trie's content in [origin, last key] */
+#define KH_RANGE_BAD_ORDER 1   /* keys not strictly ascending, first key < origin, or an empty value */
+#define KH_RANGE_MISSING 2     /* a hash on a boundary path is not in the node set (missing32) */
+#define KH_RANGE_BAD_NODE 3    /* a node met on a boundary path is not a well-formed trie node */
+#define KH_RANGE_BAD_ROOT 4    /* the rebuilt root differs from the given one */
+#define KH_RANGE_INCOMPLETE 5  /* no entries, yet the proof shows a key at or after origin */
+int kh_verify_ranges(const uint8_t* roots32, const uint8_t* origins32, const uint8_t* proved, uint64_t nr,
+                     const uint8_t* keys32, const uint8_t* vals, const uint64_t* voff, const uint64_t* ent_off,
+                     const uint8_t* enc, const uint64_t* off, uint64_t n_nodes,
+                     uint8_t* status, uint8_t* more, uint8_t* missing32);
+int kh_dev_verify_ranges(kh_ctx* ctx, const uint8_t* d_roots32, const uint8_t* d_origins32, const uint8_t* d_proved,
+                         uint64_t nr, const uint8_t* d_keys32, const uint8_t* d_vals, const uint64_t* d_voff,
+                         const uint64_t* d_ent_off, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n_nodes,
+                         uint8_t* status, uint8_t* more, uint8_t* missing32);
 
 /* HBM held by a resident trie or forest.  Records and the value heap are append-only between
  * compactions: a commit appends the records and values it makes and leaves the ones it

@@ -1431,6 +1431,69 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_verifyProofs(JNIEnv* env, jclas
   return (jlong)need;
 }
 
+/* Range responses checked against their roots without a handle (kh_verify_ranges): the receiving
+ * half of range + prove(KH_PROVE_TRIE_KEYS).  nr = entOff.length - 1 ranges over ONE node set
+ * (nNodes encodings in enc / off): roots (32 bytes a range), origins (32 bytes a range, or null:
+ * all zero), proved (a byte a range: 0 the entries claim to be the whole trie, 1 a boundary proof is
+ * used), the entries' 32-byte trie keys with their values packed in vals / voff, range s holding
+ * entries entOff[s] .. entOff[s + 1].  Out: status (KH_RANGE_*) and more, a byte a range, and
+ * missing (32 bytes a range, or null: the absent hash of a KH_RANGE_MISSING range).  Returns the
+ * number of ranges whose status is not KH_RANGE_OK. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_verifyRanges(JNIEnv* env, jclass cls, jbyteArray roots,
+                                                             jbyteArray origins, jbyteArray proved, jbyteArray keys,
+                                                             jbyteArray vals, jlongArray voff, jlongArray entOff,
+                                                             jbyteArray enc, jlongArray off, jint nNodes,
+                                                             jbyteArray status, jbyteArray more, jbyteArray missing) {
+  (void)cls;
+  /* offset arrays hold one element more than they count: never null or empty (entOff[nr] and voff[ne] are read) */
+  if (len_of(env, entOff) < 1 || len_of(env, voff) < 1) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyRanges: entOff and voff must hold at least one offset");
+    return 0;
+  }
+  const uint64_t nr = count_of(env, entOff), ne = count_of(env, voff);
+  if (nNodes < 0 || (uint64_t)len_of(env, roots) < 32 * nr || (origins && (uint64_t)len_of(env, origins) < 32 * nr) ||
+      (uint64_t)len_of(env, proved) < nr || (uint64_t)len_of(env, status) < nr || (uint64_t)len_of(env, more) < nr ||
+      (missing && (uint64_t)len_of(env, missing) < 32 * nr) || (uint64_t)len_of(env, off) < (uint64_t)nNodes + 1 ||
+      (uint64_t)len_of(env, keys) < 32 * ne) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyRanges: an array is too short for its ranges / entries");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint8_t* rt = in_b(env, &b, roots);
+  const uint8_t* og = in_b(env, &b, origins);
+  const uint8_t* pv = in_b(env, &b, proved);
+  const uint8_t* ks = in_b(env, &b, keys);
+  const uint8_t* vs = in_b(env, &b, vals);
+  const uint64_t* vo = in_l(env, &b, voff);
+  const uint64_t* eo = in_l(env, &b, entOff);
+  const uint8_t* en = in_b(env, &b, enc);
+  const uint64_t* of = in_l(env, &b, off);
+  uint8_t* st = out_buf(env, &b, status, 1);
+  uint8_t* mo = out_buf(env, &b, more, 1);
+  uint8_t* ms = out_buf(env, &b, missing, 1);
+  if (bufs_failed(env, &b)) return 0;
+  /* the library reads keys / voff up to entOff[nr], vals up to voff[ne] and enc up to off[nNodes] */
+  if (eo[nr] > ne || vo[ne] > (uint64_t)len_of(env, vals) || of[nNodes] > (uint64_t)len_of(env, enc)) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "verifyRanges: entOff / voff / off point past keys / vals / enc");
+    return 0;
+  }
+  const int rc = kh_verify_ranges(rt, og, pv, nr, ks, vs, vo, eo, en, of, (uint64_t)nNodes, st, mo, ms);
+  jlong bad = 0;
+  if (rc == KH_OK) {
+    for (uint64_t s = 0; s < nr; ++s) bad += st[s] != KH_RANGE_OK;
+    put_b(env, status, st, nr);
+    put_b(env, more, mo, nr);
+    if (missing) put_b(env, missing, ms, 32 * nr);
+  }
+  bufs_free(&b);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return bad;
+}
+
 /* ---- versions (Ledger.scala:237-271 retry / reject; TrieAccounts.rootHash; copy) ---- */
 JNIEXPORT jint JNICALL Java_khipu_trie_gpu_Khst_savepoint(JNIEnv* env, jclass cls, jlong handle) {
   (void)cls;

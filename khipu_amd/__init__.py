@@ -7,9 +7,11 @@ multi-GPU driver.
 """
 from ._lib import (DeviceError, KhError, KhStats, MPTException, MPTNodeMissingException, KH_HASH_KEYS, LIB_PATH,
                    lib)
+from .device import verify_range, verify_ranges
 from .trie import EMPTY_TRIE_HASH, MerklePatriciaTrie, kec256, kec256_batch, trie_root, trie_root_nodes, trie_roots
 
 __all__ = [
     "DeviceError", "KhError", "KhStats", "MPTException", "MPTNodeMissingException", "KH_HASH_KEYS", "LIB_PATH", "lib",
     "EMPTY_TRIE_HASH", "MerklePatriciaTrie", "kec256", "kec256_batch", "trie_root", "trie_root_nodes", "trie_roots",
+    "verify_range", "verify_ranges",
 ]

@@ -32,6 +32,13 @@ KH_PROOF_BAD_HASH = 2   # a listed node does not hash to the reference that lead
 KH_PROOF_BAD_NODE = 3   # a node on the walk is not a well-formed trie node, or a path index >= n_nodes
 KH_PROOF_SHORT = 4      # the walk reaches a hash reference and the list has no further node
 KH_PROOF_EXTRA = 5      # the walk ends before the list does
+# kh_verify_ranges statuses
+KH_RANGE_OK = 0          # the entries are exactly the trie's content in [origin, last key]
+KH_RANGE_BAD_ORDER = 1   # keys not strictly ascending, first key < origin, or an empty value
+KH_RANGE_MISSING = 2     # a hash on a boundary path is not in the node set
+KH_RANGE_BAD_NODE = 3    # a node met on a boundary path is not a well-formed trie node
+KH_RANGE_BAD_ROOT = 4    # the rebuilt root differs from the given one
+KH_RANGE_INCOMPLETE = 5  # no entries, yet the proof shows a key at or after origin
 
 # every symbol include/khst.h declares
 EXPORTS = (
@@ -49,7 +56,8 @@ EXPORTS = (
     "kh_trie_prove", "kh_verify_proofs", "kh_forest_load_nodes", "kh_forest_load_nodes_host", "kh_forest_roots",
     "kh_forest_evict", "kh_trie_open_partial", "kh_trie_open_partial_host", "kh_forest_load_partial",
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
-    "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range",
+    "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
+    "kh_dev_verify_ranges",
 )
 
 
@@ -196,6 +204,8 @@ def lib():
     L.kh_trie_range_host.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      ctypes.POINTER(i32), vp, vp]
     L.kh_dev_trie_range.argtypes = L.kh_trie_range_host.argtypes
+    L.kh_verify_ranges.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
+    L.kh_dev_verify_ranges.argtypes = [vp] + L.kh_verify_ranges.argtypes
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

@@ -708,6 +708,68 @@ def verify_proofs(roots, keys, proofs_or_table, hash_keys=False):
     raise RuntimeError("kh_verify_proofs: size negotiation failed")
 
 
+def _range_arrays(roots, origins, responses, nodes, proved):
+    """The packed arrays of a kh_verify_ranges call (numpy, kept alive by the caller)."""
+    roots, responses = list(roots), [(list(k), list(v)) for k, v in responses]
+    nr = len(roots)
+    if origins is not None:
+        origins = [o if o is not None else b"\0" * 32 for o in origins]
+    if isinstance(nodes, ProofTable):
+        nodes = nodes.nodes
+    elif isinstance(nodes, dict):
+        nodes = list(nodes.values())
+    nodes = list(nodes) if nodes is not None else []
+    if proved is None:
+        proved = [1] * nr
+    if len(responses) != nr or len(proved) != nr or (origins is not None and len(origins) != nr):
+        raise _lib.MPTException(_lib.KH_EINVAL, "one origin, response and proved flag per root")
+    keys = [k for ks, _ in responses for k in ks]
+    vals = [v for _, vs in responses for v in vs]
+    if any(len(ks) != len(vs) for ks, vs in responses) or any(len(k) != 32 for k in keys) or \
+            any(len(r) != 32 for r in roots) or (origins is not None and any(len(o) != 32 for o in origins)):
+        raise _lib.MPTException(_lib.KH_EINVAL, "keys, roots and origins are 32 bytes; one value per key")
+    a = {
+        "roots": np.frombuffer(b"".join(roots) + b"\0", np.uint8).copy(),
+        "origins": np.frombuffer(b"".join(origins) + b"\0", np.uint8).copy() if origins is not None else None,
+        "proved": np.asarray(list(proved) + [0], np.uint8),
+        "keys": np.frombuffer(b"".join(keys) + b"\0", np.uint8).copy(),
+        "vals": np.frombuffer(b"".join(vals) + b"\0", np.uint8).copy(),
+        "voff": np.zeros(len(keys) + 1, np.uint64),
+        "ent_off": np.zeros(nr + 1, np.uint64),
+        "enc": np.frombuffer(b"".join(nodes) + b"\0", np.uint8).copy(),
+        "off": np.zeros(len(nodes) + 1, np.uint64),
+    }
+    np.cumsum([len(v) for v in vals], out=a["voff"][1:])
+    np.cumsum([len(ks) for ks, _ in responses], out=a["ent_off"][1:])
+    np.cumsum([len(e) for e in nodes], out=a["off"][1:])
+    return nr, len(nodes), a
+
+
+def verify_ranges(roots, origins, responses, nodes, proved=None):
+    """kh_verify_ranges: range responses checked against their roots without a handle, many in one
+    call over ONE node set.  roots[s]: the 32-byte root; origins[s]: the 32-byte origin (origins
+    None, or an entry None: zero); responses[s] = (keys, vals), the entries in key order (32-byte
+    trie keys); nodes: a list or dict of node encodings, or the ProofTable range_proof returns;
+    proved[s] (default all 1): 0 claims the entries are the whole trie and reads no node.  Returns
+    [(status, more, missing or None)] per range: status a KH_RANGE_* code, more whether the trie
+    holds a key above the last entry, missing the absent hash when status is KH_RANGE_MISSING."""
+    nr, nn, a = _range_arrays(roots, origins, responses, nodes, proved)
+    status, more, miss = np.zeros(nr + 1, np.uint8), np.zeros(nr + 1, np.uint8), np.zeros(32 * nr + 1, np.uint8)
+    check(lib().kh_verify_ranges(a["roots"].ctypes.data, a["origins"].ctypes.data if a["origins"] is not None else None,
+                                 a["proved"].ctypes.data, nr, a["keys"].ctypes.data, a["vals"].ctypes.data,
+                                 a["voff"].ctypes.data, a["ent_off"].ctypes.data, a["enc"].ctypes.data,
+                                 a["off"].ctypes.data, nn, status.ctypes.data, more.ctypes.data, miss.ctypes.data))
+    return [(int(status[s]), bool(more[s]),
+             miss[32 * s:32 * s + 32].tobytes() if status[s] == _lib.KH_RANGE_MISSING else None) for s in range(nr)]
+
+
+def verify_range(root, origin, keys, vals, nodes):
+    """One range through verify_ranges: (status, more, missing or None).  nodes None: the entries
+    claim to be the whole trie (proved = 0)."""
+    return verify_ranges([root], [origin], [(keys, vals)], nodes if nodes is not None else [],
+                         [0 if nodes is None else 1])[0]
+
+
 def emitted_nodes(call):
     """Size negotiation of kh_trie_emit_nodes (KH_ENOSPC reports the sizes; no re-encoding).
     Another thread's commit on the handle may replace the set between the size query and the
