@@ -670,6 +670,49 @@ int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], con
                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32],
                       uint8_t missing32[32]);
 
+/* ---- batched range scan: many key ranges of a forest (or of one trie) in one call ----
+ * nq requests answered in request order under ONE entry and byte budget (the serving half of a
+ * GetStorageRanges response, which kh_verify_ranges checks in one call).  Request q is trie
+ * tries[q] (forests; on a single trie `tries` is ignored and may be NULL; an id the forest does not
+ * hold: an empty request; the same trie may be named by several requests) and the range
+ * [origins32[32q..), limits32[32q..)], both inclusive (origins32 NULL: every origin 32 zero bytes;
+ * limits32 NULL: every limit 32 bytes of 0xFF; origin > limit: an empty request).  Keys are TRIE
+ * keys, as in kh_trie_range_host.
+ *   The answer is the concatenation, in request order, of each request's entries in ascending key
+ * order, cut to its longest prefix of at most max_entries entries IN TOTAL whose values fit
+ * val_cap IN TOTAL.  keys32 holds 32 * max_entries bytes, voff max_entries + 1 slots, ent_off
+ * nq + 1 slots: entry i is keys32[32i..) with the value vals[voff[i]..voff[i+1]); request q's
+ * entries are ent_off[q] .. ent_off[q+1], and ent_off[nq] = *n_entries.
+ *   *n_done is the number of leading requests answered completely; *n_done == nq: everything asked
+ * for was returned.  Otherwise request *n_done is the cut one: its entries so far are returned
+ * (none when the cut falls exactly on its first entry), next32 is its first key not returned
+ * (continue with that as its origin), and the requests after it are unanswered -- their spans are
+ * empty and they are to be asked again.  Empty requests before the cut one count as done.
+ *   No cursor and no epoch; read-only on the handle; with a savepoint open a call reads the commits
+ * since, as the single call does.  All requests move through the rounds of the walk together: a
+ * call costs the rounds of its deepest request, and its work and memory follow max_entries + nq,
+ * not the tries' sizes (khipu_amd/csrc/range.h).
+ *   KH_ENOSPC  not even the first entry of the whole answer fits: *val_bytes is its size, nothing
+ *              else is written
+ *   KH_EINVAL  nq == 0, max_entries == 0, nq + max_entries >= 2^31, a null output, or `tries` NULL
+ *              on a forest
+ *   KH_ENODE   (partial handles only) a missing subtree is among the first max_entries + 1 things of
+ *              the concatenated answer, a missing subtree that meets its request's range counting
+ *              as one thing at its lowest key: missing32 (nullable) is the hash of its node and
+ *              *n_done the index of the request it belongs to (which trie's store to fetch for);
+ *              nothing else is written
+ * _host form with host buffers; kh_dev_trie_ranges with tries / origins32 / limits32 / keys32 /
+ * vals / voff / ent_off device buffers (voff and ent_off 8-byte aligned), on the handle's context
+ * stream (the scalar outputs are host words, valid on return). */
+int kh_trie_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* origins32, const uint8_t* limits32,
+                        uint64_t nq, uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap,
+                        uint64_t* voff, uint64_t* ent_off, uint64_t* n_entries, uint64_t* val_bytes,
+                        uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]);
+int kh_dev_trie_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins32, const uint8_t* d_limits32,
+                       uint64_t nq, uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap,
+                       uint64_t* d_voff, uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes,
+                       uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]);
+
 /* ---- range verification: range responses checked against a root, without a handle ----
  * The receiving half of kh_trie_range_host + kh_trie_prove(KH_PROVE_TRIE_KEYS) (snap's ranges,
  * geth's VerifyRangeProof), nr ranges a call over ONE node set.  Range s: root roots32[32s..),

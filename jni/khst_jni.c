@@ -1375,6 +1375,67 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_range(JNIEnv* env, jclass cls, 
   return (jlong)ne;
 }
 
+/* Many ranges in one call (kh_trie_ranges_host): nq requests -- trie tries[q] (forests; null on a
+ * single trie), range [origins[32q..), limits[32q..)] (either array null: the lowest / the highest
+ * key for every request) -- answered in request order under ONE budget: at most
+ * min(keys.length / 32, voff.length - 1) entries in total, with values fitting vals in total.  The
+ * entries go into keys / vals / voff as in range; request q's entries are entOff[q] .. entOff[q+1]
+ * (entOff holds nq + 1).  sizes[0] = entries, sizes[1] = value bytes, sizes[2] = the number of
+ * leading requests answered completely: when it is less than nq, that request is the cut one, next
+ * (byte[32]) its first key not returned, and the requests after it are to be asked again.  Returns
+ * the entry count, or -1 when vals cannot hold even the first value (sizes[1] is its size).  A
+ * partial handle whose answer meets a missing subtree throws MPTNodeMissingException with the hash
+ * to fetch, sizes[2] the request it belongs to. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_ranges(JNIEnv* env, jclass cls, jlong handle, jintArray tries,
+                                                       jbyteArray origins, jbyteArray limits, jint nq,
+                                                       jbyteArray keys, jbyteArray vals, jlongArray voff,
+                                                       jlongArray entOff, jbyteArray next, jlongArray sizes) {
+  (void)cls;
+  if (nq <= 0 || (tries && len_of(env, tries) < nq) || (origins && (uint64_t)len_of(env, origins) < 32ull * (uint64_t)nq) ||
+      (limits && (uint64_t)len_of(env, limits) < 32ull * (uint64_t)nq) || len_of(env, entOff) < nq + 1 ||
+      len_of(env, next) < 32) {
+    throw_cls(env, "java/lang/IllegalArgumentException",
+              "ranges: nq must be positive; tries / origins / limits / entOff must hold nq requests, next 32 bytes");
+    return 0;
+  }
+  uint64_t max_entries = (uint64_t)len_of(env, keys) / 32;
+  const jsize nvo = len_of(env, voff);
+  if ((uint64_t)(nvo > 0 ? nvo - 1 : 0) < max_entries) max_entries = (uint64_t)(nvo > 0 ? nvo - 1 : 0);
+  if (max_entries == 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "ranges: keys / voff hold no entry");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint32_t* tr = in_i(env, &b, tries);
+  const uint8_t* og = in_b(env, &b, origins);
+  const uint8_t* lm = in_b(env, &b, limits);
+  uint8_t* ks = out_buf(env, &b, keys, 1);
+  uint8_t* vs = out_buf(env, &b, vals, 1);
+  uint64_t* vo = out_buf(env, &b, voff, 8);
+  uint64_t* eo = out_buf(env, &b, entOff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t ne = 0, nb = 0, nd = 0;
+  uint8_t nx[32] = {0}, miss[32] = {0};
+  const int rc = kh_trie_ranges_host(H(handle), tr, og, lm, (uint64_t)nq, max_entries, ks, vs,
+                                     (uint64_t)len_of(env, vals), vo, eo, &ne, &nb, &nd, nx, miss);
+  if (rc == KH_OK) {
+    put_b(env, keys, ks, 32 * ne);
+    put_b(env, vals, vs, nb);
+    put_l(env, voff, vo, ne + 1);
+    put_l(env, entOff, eo, (uint64_t)nq + 1);
+    if (nd < (uint64_t)nq) put_b(env, next, nx, 32);
+  }
+  bufs_free(&b);
+  const jlong sz[3] = {(jlong)ne, (jlong)nb, (jlong)nd};
+  put_l(env, sizes, sz, 3);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh_hash(env, rc, miss);
+    return 0;
+  }
+  return (jlong)ne;
+}
+
 /* The proofs prove returned (or a peer sent) checked against roots (32 bytes: one root for every
  * key; or 32 per key): status[i] one of KH_PROOF_*, the values of the KH_PROOF_VALUE keys packed
  * into vals with voff[n + 1].  nNodes table nodes in rlp / off.  flags: KH_HASH_KEYS.  Returns the

@@ -57,7 +57,7 @@ EXPORTS = (
     "kh_forest_evict", "kh_trie_open_partial", "kh_trie_open_partial_host", "kh_forest_load_partial",
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
-    "kh_dev_verify_ranges",
+    "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges",
 )
 
 
@@ -204,6 +204,9 @@ def lib():
     L.kh_trie_range_host.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      ctypes.POINTER(i32), vp, vp]
     L.kh_dev_trie_range.argtypes = L.kh_trie_range_host.argtypes
+    L.kh_trie_ranges_host.argtypes = [vp, vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, ctypes.POINTER(u64),
+                                      ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp]
+    L.kh_dev_trie_ranges.argtypes = L.kh_trie_ranges_host.argtypes
     L.kh_verify_ranges.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
     L.kh_dev_verify_ranges.argtypes = [vp] + L.kh_verify_ranges.argtypes
     for name in EXPORTS:

@@ -20,8 +20,33 @@
 //   the end   a round in which no item was a branch leaves the answer: entries and stubs in
 //             range, in key order (at most 64 branch depths and the closing round)
 //
+// MANY RANGES A CALL (kh_trie_ranges_host, kh_dev_trie_ranges): nq requests (trie, origin, limit)
+// answered in request order under one entry and byte budget.  The frontier is SEGMENTED: an item
+// is (record, request), ordered by (request, key).  Round 0 holds the root record of every request
+// (NONE for an empty one), request q at place q; a round selects every item against ITS OWN
+// request's KeyRange (an nq-long array), and the fill writes the item's request beside each child
+// it places, so a segment's children stay together, in key order, between those of the requests
+// either side: the order holds by construction, with no atomic claiming a slot.  All requests move
+// through the rounds together, so a call takes the rounds of its deepest request.
+//   the cut   the new frontier is the first max_entries + 2 * nq items.  Subtrees are disjoint and
+//             ordered.  Per request at most one item lies on origin's path and at most one on
+//             limit's, either may turn out empty, and limit's is the last of its segment; every
+//             other item holds an entry (or a stub: one thing).  Let X be the item that holds thing
+//             max_entries + 1 of the concatenated answer, in request x.  The empty items before X
+//             are at most two for each of the x <= nq - 1 requests before x and the origin item of
+//             x (its limit item is X or lies after X): 2 * nq - 1.  The items up to X that hold a
+//             thing are at most max_entries + 1.  So X is among the first max_entries + 2 * nq
+//             items, and what lies past them is never needed.  One item fewer can lose X: the cut
+//             in the last request, both boundary items of every request empty, every other item
+//             one entry (tests/test_ranges_host.py builds that input).
+//   the end   a round in which no item of any request was a branch: at most 64 branch depths and
+//             the closing round, whatever nq is.  Then the first max_entries + 1 things, the
+//             lowest stub, the fit to val_cap and the write are the single call's; ent_off[q] is
+//             the lower bound of q in the returned items' (non-decreasing) requests, and the cut
+//             request is that of thing k, the first not returned.
+//
 // KH_HD bodies only, shared by range_kernels.hip (16 lanes an item, lane c owning child c, as
-// export.h) and the host replay of tests/range_host.
+// export.h) and the host replays of tests/range_host and tests/ranges_host.
 #pragma once
 #include "export.h"
 
@@ -64,11 +89,15 @@ KH_HD uint32_t rng_count(uint32_t sel) { return kh_popc(sel & 0xFFFFu) + (sel >>
 
 // lane c of item r (selection sel, scanned base): the item itself (lane 0) or child c goes to its
 // place in the next frontier when that place lies before the cut; false: the anchor map lacks a
-// child the mask names (a corrupt map)
+// child the mask names (a corrupt map).  outq (a segmented frontier): the item's request q is
+// written beside what is placed.
 KH_HD bool rng_fill_lane(const Recs& R, const AMap& M, uint32_t r, uint32_t sel, uint32_t c, uint64_t base,
-                         uint64_t cut, uint32_t* out) {
+                         uint64_t cut, uint32_t* out, uint32_t* outq = nullptr, uint32_t q = 0) {
   if (sel & RNG_SELF) {
-    if (c == 0 && base < cut) out[base] = r;
+    if (c == 0 && base < cut) {
+      out[base] = r;
+      if (outq) outq[base] = q;
+    }
     return true;
   }
   if (!((sel >> c) & 1)) return true;
@@ -76,7 +105,33 @@ KH_HD bool rng_fill_lane(const Recs& R, const AMap& M, uint32_t r, uint32_t sel,
   if (at >= cut) return true;
   const uint32_t child = exp_child(R, M, r, c);
   out[at] = child;
+  if (outq) outq[at] = q;
   return child != NONE;
+}
+
+// ---- many ranges a call
+// request q's range from the packed origins and limits (either NULL: all zero / all 0xFF; byte
+// reads, so the arrays need no alignment); false: origin > limit, an empty request
+KH_HD bool rng_request(const uint8_t* origins32, const uint8_t* limits32, uint64_t q, KeyRange* g) {
+  uint8_t *o = (uint8_t*)g->o, *l = (uint8_t*)g->l;
+  for (int b = 0; b < 32; ++b) {
+    o[b] = origins32 ? origins32[32 * q + b] : (uint8_t)0;
+    l[b] = limits32 ? limits32[32 * q + b] : (uint8_t)0xFF;
+  }
+  return key_cmp(g->o, g->l) <= 0;
+}
+// the first of the n returned items whose request is q or later (iq does not decrease): where
+// request q's entries start
+KH_HD uint64_t rng_ent_off(const uint32_t* iq, uint64_t n, uint64_t q) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (iq[mid] < q)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
 }
 
 // ---- after the last round: the frontier's items are entries (leaves, value-only branches) or stubs

@@ -489,6 +489,18 @@ class ResidentTrie(_Versioned):
         self.ctx._sync()
         return _range_proof(self.h, origin, limit, max_entries, val_cap, None)
 
+    def ranges(self, requests, max_entries=1024, val_cap=1 << 20):
+        """Many ranges of the trie in one call (kh_trie_ranges_host; trie_ranges): requests =
+        [(origin or None, limit or None)] -> (pages, n_done, next), pages[q] = (keys, vals)."""
+        self.ctx._sync()
+        return trie_ranges(self.h, requests, max_entries, val_cap)
+
+    def ranges_proof(self, requests, max_entries=1024, val_cap=1 << 20):
+        """ranges() plus ONE shared ProofTable for every request that needs a boundary proof, and the
+        proved flags: (pages, n_done, next, table, proved), as verify_ranges takes them."""
+        self.ctx._sync()
+        return _ranges_proof(self.h, requests, max_entries, val_cap, False)
+
     @property
     def root_hash(self):
         return self.root
@@ -597,6 +609,86 @@ def _range_proof(h, origin, limit, max_entries, val_cap, trie):
             keys[-1] if keys else (limit if limit is not None else b"\xff" * 32)]
     _, table = trie_prove(h, ends, None if trie is None else [trie, trie], shared=True, trie_keys=True)
     return keys, vals, more, nxt, table
+
+
+def trie_ranges(h, requests, max_entries=1024, val_cap=1 << 20, forest=False):
+    """Many ranges in one call (kh_trie_ranges_host).  requests: [(trie_id, origin, limit)] on a
+    forest, [(origin, limit)] on a single trie (origin / limit None: the lowest / the highest key).
+    -> (pages, n_done, next): pages[q] = (keys, vals) of request q, the requests answered in order
+    under max_entries entries and val_cap value bytes IN TOTAL; n_done leading requests are answered
+    completely; when n_done < len(requests), request n_done is the cut one, next its first key not
+    returned (else None), and the requests after it are unanswered (empty pages).  Keys are trie
+    keys.  KH_ENOSPC raises KhError with .val_bytes; KH_ENODE raises MPTNodeMissingException with
+    the hash to fetch in .missing and the request it belongs to in .request."""
+    reqs = [tuple(q) for q in requests]
+    if not forest:
+        reqs = [(0, o, l) for o, l in reqs]
+    nq = len(reqs)
+    n = int(max_entries)
+    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
+    if any(x is not None and len(x) != 32 for _, o, l in reqs for x in (o, l)):
+        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
+    tb = np.asarray([t for t, _, _ in reqs] + [0], np.uint32) if forest else None
+    ob = lb = None
+    if any(o is not None for _, o, _ in reqs):
+        ob = np.frombuffer(b"".join(o if o is not None else b"\0" * 32 for _, o, _ in reqs), np.uint8).copy()
+    if any(l is not None for _, _, l in reqs):
+        lb = np.frombuffer(b"".join(l if l is not None else b"\xff" * 32 for _, _, l in reqs), np.uint8).copy()
+    keys = np.zeros(32 * room, np.uint8)
+    vals = np.zeros(max(int(val_cap), 1), np.uint8)
+    voff = np.zeros(room + 1, np.uint64)
+    eoff = np.zeros(nq + 1, np.uint64)
+    ne, vb, nd = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    nxt = np.zeros(32, np.uint8)
+    miss = np.zeros(32, np.uint8)
+    rc = lib().kh_trie_ranges_host(h, tb.ctypes.data if tb is not None else None,
+                                   ob.ctypes.data if ob is not None else None,
+                                   lb.ctypes.data if lb is not None else None, nq, n, keys.ctypes.data,
+                                   vals.ctypes.data, int(val_cap), voff.ctypes.data, eoff.ctypes.data,
+                                   ctypes.byref(ne), ctypes.byref(vb), ctypes.byref(nd), nxt.ctypes.data,
+                                   miss.ctypes.data)
+    if rc == _lib.KH_ENODE:
+        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+        e.missing = miss.tobytes()
+        e.request = int(nd.value)
+        raise e
+    if rc == _lib.KH_ENOSPC:
+        e = _lib.KhError(rc, lib().kh_last_error().decode())
+        e.val_bytes = int(vb.value)
+        raise e
+    check(rc)
+    assert int(eoff[nq]) == int(ne.value)
+    kb, vbuf = keys[:32 * int(ne.value)].tobytes(), vals[:int(vb.value)].tobytes()
+    pages = [([kb[32 * i:32 * i + 32] for i in range(int(eoff[q]), int(eoff[q + 1]))],
+              [vbuf[int(voff[i]):int(voff[i + 1])] for i in range(int(eoff[q]), int(eoff[q + 1]))]) for q in range(nq)]
+    done = int(nd.value)
+    return pages, done, nxt.tobytes() if done < nq else None
+
+
+def _ranges_proof(h, requests, max_entries, val_cap, forest):
+    """trie_ranges and the boundary proofs its response carries, in ONE shared table of one
+    kh_trie_prove(KH_PROVE_TRIE_KEYS | KH_PROVE_SHARED) call: proved[q] = 1 for the cut request and
+    for every answered request whose origin is not zero or whose limit is not all-0xFF, each proved
+    over [origin, its last returned key, or its limit when it returned none].
+    -> (pages, n_done, next, table, proved)"""
+    reqs = [tuple(q) for q in requests]
+    pages, done, nxt = trie_ranges(h, reqs, max_entries, val_cap, forest)
+    if not forest:
+        reqs = [(0, o, l) for o, l in reqs]
+    zero, ff = b"\0" * 32, b"\xff" * 32
+    proved, ends, ids = [], [], []
+    for q, (t, o, l) in enumerate(reqs):
+        o, l = o if o is not None else zero, l if l is not None else ff
+        p = q == done or (q < done and (o != zero or l != ff))
+        proved.append(int(p))
+        if p:
+            ends += [o, pages[q][0][-1] if pages[q][0] else l]
+            ids += [t, t]
+    if ends:
+        _, table = trie_prove(h, ends, ids if forest else None, shared=True, trie_keys=True)
+    else:
+        table = ProofTable([], [], [], [0])
+    return pages, done, nxt, table, proved
 
 
 class ProofTable:
@@ -942,6 +1034,18 @@ class ResidentForest(_Versioned):
         """ResidentTrie.range_proof for one trie of the forest."""
         self.ctx._sync()
         return _range_proof(self.h, origin, limit, max_entries, val_cap, trie)
+
+    def ranges(self, requests, max_entries=1024, val_cap=1 << 20):
+        """Many ranges in one call (kh_trie_ranges_host; trie_ranges): requests = [(trie_id, origin or
+        None, limit or None)] -> (pages, n_done, next), pages[q] = (keys, vals)."""
+        self.ctx._sync()
+        return trie_ranges(self.h, requests, max_entries, val_cap, forest=True)
+
+    def ranges_proof(self, requests, max_entries=1024, val_cap=1 << 20):
+        """ranges() plus ONE shared ProofTable for every request that needs a boundary proof, and the
+        proved flags: (pages, n_done, next, table, proved), as verify_ranges takes them."""
+        self.ctx._sync()
+        return _ranges_proof(self.h, requests, max_entries, val_cap, True)
 
     def last_roots(self):
         """{trie_id: root} of the last commit (kh_forest_last_roots; also after block_commit)."""
