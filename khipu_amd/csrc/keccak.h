@@ -150,6 +150,80 @@ KH_HD void keccakf(KState& s) {
 
 KH_HD uint64_t lane(const KState& s, int i) { return ((uint64_t)s.hi[i] << 32) | s.lo[i]; }
 
+// ---- The digest form.  A Keccak-256 digest is lanes 0..3 of the final state, so the last round
+// owes only those: all five column parities, but theta-apply / rho / pi for the five lanes that
+// pi sends to row 0 (the diagonal 0, 6, 12, 18, 24), chi for lanes 0..3, and iota: 62 VALU and
+// 18 funnel shifts instead of 180 and 58.  Lanes 4..24 are left as they were (not a Keccak state).
+// Straight-line code gets this from the compiler's dead-code elimination (the leaf kernel); a
+// permutation that ends inside a loop does not.
+KH_HD void keccak_round_digest(KState& S, uint64_t rc) {
+  constexpr int ROT[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
+  uint32_t CL[5], CH[5], RL[5], RH[5], BL[5], BH[5];
+#pragma unroll
+  for (int x = 0; x < 5; ++x) {
+    CL[x] = xor3(xor3(S.lo[x], S.lo[x + 5], S.lo[x + 10]), S.lo[x + 15], S.lo[x + 20]);
+    CH[x] = xor3(xor3(S.hi[x], S.hi[x + 5], S.hi[x + 10]), S.hi[x + 15], S.hi[x + 20]);
+  }
+#pragma unroll
+  for (int x = 0; x < 5; ++x) {
+    uint32_t rl = CL[x], rh = CH[x];
+    rotl_hl(rl, rh, 1);
+    RL[x] = rl;
+    RH[x] = rh;
+  }
+#pragma unroll
+  for (int x = 0; x < 5; ++x) {  // B[x] of row 0 comes from lane (x, y = x): y + 5 * ((2x + 3y) % 5) == x
+    const int i = 6 * x;
+    uint32_t l = xor3(S.lo[i], CL[(x + 4) % 5], RL[(x + 1) % 5]);
+    uint32_t h = xor3(S.hi[i], CH[(x + 4) % 5], RH[(x + 1) % 5]);
+    rotl_hl(l, h, ROT[i]);
+    BL[x] = l;
+    BH[x] = h;
+  }
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    S.lo[x] = BL[x] ^ (~BL[x + 1] & BL[(x + 2) % 5]);
+    S.hi[x] = BH[x] ^ (~BH[x + 1] & BH[(x + 2) % 5]);
+  }
+  S.lo[0] ^= (uint32_t)rc;
+  S.hi[0] ^= (uint32_t)(rc >> 32);
+}
+
+// The permutation of a final block: round 0 outside the loop (state words that are compile-time
+// constants -- the zero capacity, a fixed-length message's zero words and padding -- fold out of
+// its parities and most of its theta), rounds 1..22 as a loop of U per iteration (U divides 22),
+// the digest round last.  Only lanes 0..3 of the result are defined.
+// U = 22, straight-line, by default: key hashing at 100M 10.25 -> 9.65 ms; as 1 + 2 x 11 + 1 the
+// table loads' address arithmetic and waits (4-byte scalar instructions) are spread through the
+// loop body and leave 29 % of its VALU instructions in the slow code placement: 10.0 ms
+// (profiles/key_hash_digest_ab_100m.jsonl)
+#ifndef KECCAK_DIGEST_LOOP_ROUNDS
+#define KECCAK_DIGEST_LOOP_ROUNDS 22  // straight-line (measurement builds: 11 is a loop of two iterations)
+#endif
+constexpr int KECCAK_DIGEST_LOOP = KECCAK_DIGEST_LOOP_ROUNDS;
+// The round constants as values: straight-line code takes them as instruction literals (no
+// scalar loads or waits inside the permutation; iota is then an 8-byte VALU instruction like the
+// rest of the round, so the whole permutation keeps one code placement).
+KH_HD uint64_t round_constant_imm(int r) {
+  constexpr uint64_t RC[24] = {
+      0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808AULL, 0x8000000080008000ULL,
+      0x000000000000808BULL, 0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL,
+      0x000000000000008AULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000AULL,
+      0x000000008000808BULL, 0x800000000000008BULL, 0x8000000000008089ULL, 0x8000000000008003ULL,
+      0x8000000000008002ULL, 0x8000000000000080ULL, 0x000000000000800AULL, 0x800000008000000AULL,
+      0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
+  return RC[r];
+}
+template <int U = KECCAK_DIGEST_LOOP>
+KH_HD void keccakf_digest(KState& s) {
+  static_assert(22 % U == 0, "rounds 1..22 in whole iterations");
+  constexpr bool IMM = U == 22;
+  keccak_round(s, IMM ? round_constant_imm(0) : round_constant(0));
+#pragma unroll U
+  for (int r = 1; r < 23; ++r) keccak_round(s, IMM ? round_constant_imm(r) : round_constant(r));
+  keccak_round_digest(s, IMM ? round_constant_imm(23) : round_constant(23));
+}
+
 // ---- Keccak-f on a lane pair (k_branch_small: levels of 8k-32k branches, a wave or two per
 // SIMD, where one thread's permutation -- 180 dependent VALU a round at 4 cycles each -- is the
 // level's latency).  Lane 2i holds the low halves of the 25 state words, lane 2i + 1 the high
@@ -288,6 +362,89 @@ KH_HD void kec256_short(const uint8_t* p, uint32_t len, uint64_t out[4]) {
   out[1] = lane(s, 1);
   out[2] = lane(s, 2);
   out[3] = lane(s, 3);
+}
+
+// ---- the same hashes ending in the digest form (key hashing: k_hash_keys_ck)
+KH_HD void digest_out(const KState& s, uint64_t out[4]) {
+  out[0] = lane(s, 0);
+  out[1] = lane(s, 1);
+  out[2] = lane(s, 2);
+  out[3] = lane(s, 3);
+}
+
+// kec256_msg with the last block's permutation in the digest form
+template <bool ALIGNED>
+KH_HD void kec256_msg_digest(const uint8_t* p, uint32_t len, uint64_t out[4]) {
+  KState s = {};
+  uint32_t nfull = len / 136;
+  for (uint32_t b = 0; b < nfull; ++b) {
+#pragma unroll
+    for (int i = 0; i < 17; ++i) kxor(s, i, ALIGNED ? ((const uint64_t*)p)[i] : load64u_n(p + 8 * i, 8));
+    keccakf(s);
+    p += 136;
+  }
+  uint32_t rem = len - nfull * 136;  // [0, 135]
+#pragma unroll
+  for (int i = 0; i < 17; ++i) {
+    uint64_t w = 0;
+    uint32_t base = 8u * (uint32_t)i;
+    if (base < rem) {
+      uint32_t nb = rem - base < 8 ? rem - base : 8;
+      w = ALIGNED ? ((const uint64_t*)p)[i] : load64u_n(p + base, nb);
+      w &= low_bytes_mask(nb);
+    }
+    if ((rem >> 3) == (uint32_t)i) w ^= 0x01ULL << (8 * (rem & 7));
+    if (i == 16) w ^= 0x80ULL << 56;
+    kxor(s, i, w);
+  }
+  keccakf_digest(s);
+  digest_out(s, out);
+}
+
+// kec256_short (len <= 135, any alignment) with its one permutation in the digest form
+KH_HD void kec256_short_digest(const uint8_t* p, uint32_t len, uint64_t out[4]) {
+  KState s = {};
+#pragma unroll
+  for (int i = 0; i < 17; ++i) {
+    uint64_t w = 0;
+    const uint32_t base = 8u * (uint32_t)i;
+    if (base < len) {
+      const uint32_t nb = len - base < 8 ? len - base : 8;
+      w = load64u_n(p + base, nb) & low_bytes_mask(nb);
+    }
+    if ((len >> 3) == (uint32_t)i) w ^= 0x01ULL << (8 * (len & 7));
+    if (i == 16) w ^= 0x80ULL << 56;
+    s.lo[i] = (uint32_t)w;
+    s.hi[i] = (uint32_t)(w >> 32);
+  }
+  keccakf_digest(s);
+  digest_out(s, out);
+}
+
+// kec256 of exactly LEN bytes (LEN <= 135: one block) at any alignment, LEN a compile-time
+// constant: the words past the message are constants (zero, the 0x01 / 0x80 padding), so round 0
+// of keccakf_digest, which sits outside its loop, folds them (a 20-byte address: 3 message words
+// of 25).  The loads are kec256_short's: aligned 8-byte words, nothing read outside the message's
+// aligned span.
+template <uint32_t LEN>
+KH_HD void kec256_fixed(const uint8_t* p, uint64_t out[4]) {
+  static_assert(LEN <= 135, "one block");
+  KState s = {};
+#pragma unroll
+  for (int i = 0; i < 17; ++i) {
+    constexpr uint32_t full = LEN / 8, tail = LEN % 8;
+    uint64_t w = 0;
+    if ((uint32_t)i < full)
+      w = load64u_n(p + 8 * i, 8);
+    else if ((uint32_t)i == full && tail)
+      w = load64u_n(p + 8 * i, tail) & low_bytes_mask(tail);
+    if ((uint32_t)i == full) w ^= 0x01ULL << (8 * tail);
+    if (i == 16) w ^= 0x80ULL << 56;
+    s.lo[i] = (uint32_t)w;
+    s.hi[i] = (uint32_t)(w >> 32);
+  }
+  keccakf_digest(s);
+  digest_out(s, out);
 }
 
 KH_HD uint32_t perms_for_len(uint32_t len) { return len / 136 + 1; }

@@ -154,18 +154,28 @@ __device__ __forceinline__ uint32_t ck_word(uint64_t h0, const uint32_t* seg, ui
   const uint32_t kb = (uint32_t)(bswap64(h0) >> 32);
   return sb ? (seg[i] << (32 - sb)) | (kb >> sb) : kb;
 }
-template <bool SHORT>
+// The permutation ends in the digest round (keccak.h: the last round owes lanes 0..3 only).
+// KLEN != 0: the key length as a compile-time constant (klen == KLEN), for the two lengths the
+// callers use -- 20-byte addresses and 32-byte storage slot words: the message's constant words
+// fold out of round 0.  KLEN == 0: any length, from klen.
+template <bool SHORT, uint32_t KLEN = 0>
 __global__ void __launch_bounds__(BS) KH_KEYS_WAVES k_hash_keys_ck(const uint8_t* keys, uint32_t klen, uint64_t first,
                                                                     uint64_t n, uint64_t* out, uint32_t* ck, uint32_t* idx,
                                                                     const uint32_t* seg, uint32_t sb) {
+  // code placement: the straight-line permutation is 8-byte VALU instructions throughout,
+  // so the kernel's prologue decides whether they all sit at 4 mod 8 (fast) or 0 mod 8; the 20-byte
+  // form's leaves them 4 bytes off, and one s_nop moves them back (tests/test_code_layout.py)
+  if (KLEN == 20) asm volatile("s_nop 0");
   // keys [first, n): one launch over all of them, or one per part of host inputs still arriving
   uint64_t i = first + (uint64_t)blockIdx.x * BS + threadIdx.x;
   if (i >= n) return;
   uint64_t h[4];
-  if (SHORT)  // keys of <= 135 bytes (addresses, slot words): one block
-    kec256_short(keys + i * klen, klen, h);
+  if (KLEN)
+    kec256_fixed<KLEN>(keys + i * KLEN, h);
+  else if (SHORT)  // keys of <= 135 bytes: one block
+    kec256_short_digest(keys + i * klen, klen, h);
   else
-    kec256_msg<false>(keys + i * klen, klen, h);
+    kec256_msg_digest<false>(keys + i * klen, klen, h);
   for (int j = 0; j < 4; ++j) out[4 * i + j] = h[j];
   ck[i] = ck_word(h[0], seg, sb, i);
   idx[i] = (uint32_t)i;
@@ -2469,7 +2479,13 @@ static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats*
     for (uint32_t p = 0; p < parts; ++p) {
       const uint64_t a = A.hs && p ? A.hs->kend[p - 1] : 0, b = A.hs ? A.hs->kend[p] : n;
       if (A.hs) A.hs->stream_wait(st, p);
-      if (A.klen <= 135)
+      if (A.klen == 20)  // (addresses)
+        hipLaunchKernelGGL((k_hash_keys_ck<true, 20>), GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0,
+                           S.idx0, A.seg, sb);
+      else if (A.klen == 32)  // (storage slot words)
+        hipLaunchKernelGGL((k_hash_keys_ck<true, 32>), GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0,
+                           S.idx0, A.seg, sb);
+      else if (A.klen <= 135)
         hipLaunchKernelGGL(k_hash_keys_ck<true>, GRID(b - a, BS), dim3(BS), 0, st, A.keys, A.klen, a, b, K32, c0,
                            S.idx0, A.seg, sb);
       else
