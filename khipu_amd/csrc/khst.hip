@@ -37,38 +37,18 @@
 #include "forest.h"
 #include "nodedata.h"
 #include "layout.h"
-#include "export.h"
-#include "prove.h"
-#include "load.h"
-#include "range.h"
+#include "host.h"
 
 using namespace khst;
 
 // ---------------------------------------------------------------------------
-// errors
+// errors (host.h: KhError, HIPCHK, API_TRY; the thread's message for kh_last_error lives here)
 // ---------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int set_err(int code, const std::string& msg) {
+int khst::set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-struct KhError {
-  int code;
-  std::string msg;
-};
-#define HIPCHK(x)                                                                                  \
-  do {                                                                                             \
-    hipError_t e_ = (x);                                                                           \
-    if (e_ != hipSuccess) {                                                                        \
-      (void)hipGetLastError(); /* clear it, or the next launch check reports it again */           \
-      throw KhError{e_ == hipErrorOutOfMemory ? KH_ENOMEM : KH_EDEVICE,                            \
-                    std::string(#x) + ": " + hipGetErrorString(e_)};                               \
-    }                                                                                              \
-  } while (0)
-#define LAUNCH_CHECK() HIPCHK(hipGetLastError())
-
-#define GRID(n, bs) dim3((unsigned)(((n) + (bs)-1) / (bs)))
-constexpr int BS = 256;
 
 // ---------------------------------------------------------------------------
 // kernels
@@ -1496,7 +1476,6 @@ __global__ void __launch_bounds__(BS) k_emit_copy(Topo T, uint64_t B, const uint
   out_off[p] = boff[q];
 }
 
-
 // Copy L bytes between arbitrary byte addresses with a group of CG consecutive lanes
 // (lane = 0..CG-1): word loads (load64u_n), whole-word stores where the destination is
 // aligned, bytes at the unaligned ends.  The group's word stores are adjacent, so a
@@ -1736,119 +1715,6 @@ __global__ void __launch_bounds__(BS) k_synth_write(uint32_t cfg, uint64_t first
   synth_body_write(a, first + i, vals + voff[i]);
 }
 
-// ---------------------------------------------------------------------------
-// device workspace
-// ---------------------------------------------------------------------------
-// selects device d (d >= 0) for the guard's scope, restoring the caller's device after
-struct DevScope {
-  int prev = -1;
-  explicit DevScope(int d) {
-    int cur = -1;
-    if (d >= 0 && hipGetDevice(&cur) == hipSuccess && cur != d && hipSetDevice(d) == hipSuccess) prev = cur;
-  }
-  ~DevScope() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DevScope(const DevScope&) = delete;
-  DevScope& operator=(const DevScope&) = delete;
-};
-
-// A device buffer that remembers the GPU it lives on: growth drains and frees on THAT
-// device, and allocates on `on` (or on the current device when on < 0).
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int dev = -1;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }  // a throw between ensure() and release() does not leak HBM
-  void ensure(size_t bytes, int on = -1) {
-    if (on < 0) {
-      if (hipGetDevice(&on) != hipSuccess) on = 0;
-    }
-    if (bytes <= cap && dev == on) return;
-    if (p) {
-      // work still reading the old buffer may be in flight (kh_dev_partition_ev returns before
-      // its value copy ends): drain its device before the buffer goes (growth is rare)
-      DevScope ds(dev);
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipFree(p));
-    }
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 8 + 4096;
-    DevScope ds(on);
-    HIPCHK(hipMalloc(&p, want));
-    cap = want;
-    dev = on;
-  }
-  void release() {
-    if (p) {
-      DevScope ds(dev);
-      (void)hipFree(p);
-    }
-    p = nullptr;
-    cap = 0;
-    dev = -1;
-  }
-};
-
-// the arrays carved out of one DevBuf, each declared once (layout.h)
-[[noreturn]] static void layout_fail(const char* msg) { throw KhError{KH_EINTERNAL, msg}; }
-using Layout = BasicLayout<layout_fail>;
-static void place(DevBuf& b, const Layout& L) {
-  b.ensure(L.bytes());
-  L.place(b.p, b.cap);
-}
-
-struct BuildInfo {  // the last build's sizes, for build_stats
-  uint64_t n = 0, m = 0, B = 0, key_perms = 0, arena = 0;
-  uint32_t levels = 0;
-  bool full_sort = false, early = false, stage_ev = true;
-};
-// A host thread kept for a context (kh_block_commit's storage phase): post() hands it one job,
-// join() waits for the job; no thread is started per call.
-struct Worker {
-  std::thread th;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::function<void()> job;
-  bool has_job = false, stop = false;
-  void post(std::function<void()> f) {
-    std::unique_lock<std::mutex> lk(mu);
-    if (!th.joinable()) th = std::thread([this] { loop(); });
-    job = std::move(f);
-    has_job = true;
-    cv.notify_all();
-  }
-  void join() {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [this] { return !has_job; });
-  }
-  void loop() {
-    std::unique_lock<std::mutex> lk(mu);
-    for (;;) {
-      cv.wait(lk, [this] { return has_job || stop; });
-      if (stop) return;
-      std::function<void()> f = std::move(job);
-      lk.unlock();
-      f();  // (the job catches its own exceptions)
-      lk.lock();
-      has_job = false;
-      cv.notify_all();
-    }
-  }
-  ~Worker() {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      stop = true;
-    }
-    cv.notify_all();
-    if (th.joinable()) th.join();
-  }
-};
-
 // Host memcpy into pinned staging on COPY_THREADS host threads (the caller and COPY_THREADS - 1
 // kept workers): a single thread copies pageable -> pinned at ~22 GB/s on the box, 4 threads at
 // ~80, 8 at ~113, against ~57 GB/s of PCIe (profiles/r8a_h2d_probe.jsonl).  One job at a time,
@@ -1913,63 +1779,6 @@ class CopyPool {
   }
 };
 static CopyPool g_copy_pool;
-constexpr int RING_SLOTS = 4;
-constexpr size_t RING_CHUNK = 64u << 20;  // 64 MB chunks: 56 GB/s end to end in the probe (32-128 MB alike)
-struct kh_ctx {
-  int dev = 0;
-  int n_cu = 256;  // compute units of the device
-  hipStream_t own = nullptr;
-  hipStream_t st = nullptr;
-  hipStream_t st2 = nullptr;  // leaf hashing, concurrent with the branch topology
-  // every entry point that uses the context holds it (recursive: a *_host entry point locks,
-  // then calls its device variant, which locks again); a resident handle's calls lock the
-  // context the handle was opened on (kh_trie::home)
-  std::recursive_mutex mu;
-  DevBuf ws_list;  // element builds: the list of leaves to hash (k_leaf_prep -> k_leaf_hash_list)
-  DevBuf ws_inject;                    // kh_block_commit: the injection's error word
-  unsigned long long inject_tok = 0;   //   and the token the last call writes there on error
-  DevBuf ws_arena;  // the build's long leaves (sized once the leaves are hashed)
-  DevBuf ws1, ws2, ws3, in_keys, in_vals, in_voff, in_seg, in_kn, in_aux, in_block, out_emit, emit_dev;
-  hipEvent_t ev[11] = {};  // [0..5] build stages (st), [6] / [7] forest commit marks, [8] boundaries
-                          // ready (st), [9] / [10] leaf kernel start / end (st2)
-  unsigned long long* h_pinned = nullptr;  // small pinned staging for syncs
-  uint8_t* h_res = nullptr;                // pinned staging of the per-result outputs (grown; a pageable
-  size_t h_res_cap = 0;                    // copy of 100k roots cost 20-30 ms of page pinning per build)
-  // kh_block_commit: the second context its storage phase runs on, beside the account phase on
-  // this one, and the event of the storage roots' injection into the account bodies
-  kh_ctx* bsub = nullptr;
-  hipEvent_t bev = nullptr;
-  std::unique_ptr<Worker> bworker;
-  // plain builds on the 32-bit-prefix path do not wait for the tie kernel's flags (SortIO::
-  // speculate); a build whose flags were set (repeated keys, a long run) is redone without, and
-  // the next spec_off builds do not speculate
-  uint32_t spec_off = 0;
-  // last build (for emission)
-  Topo T{};
-  uint64_t last_B = 0;
-  uint64_t last_nres = 0;
-  BuildInfo binfo;
-  // host-input staging (HostStage): a copy stream, a ring of pinned chunks with the event of
-  // each chunk's last DMA, the events the stager records (key parts, keys + offsets, values) and
-  // the thread that streams the inputs behind the build (created on first use)
-  hipStream_t cs = nullptr;
-  uint8_t* ring = nullptr;
-  hipEvent_t ring_ev[RING_SLOTS] = {};
-  bool ring_busy[RING_SLOTS] = {};
-  uint32_t ring_next = 0;
-  std::vector<hipEvent_t> part_ev;
-  std::unique_ptr<Worker> hworker;
-  // small host inputs (a commit's ops: HostPack): packed into one pinned buffer, one DMA into
-  // in_block; pack_ev marks that DMA (the next pack waits for it before reusing the buffer)
-  uint8_t* h_pack = nullptr;
-  size_t h_pack_cap = 0;
-  hipEvent_t pack_ev = nullptr;
-  bool pack_busy = false;
-  bool pack_for_block = false;  // kh_block_commit_host -> kh_block_commit: its phases wait for pack_ev
-  // kh_verify_ranges: the staged inputs, the hashed node set, the per-range work arrays, the
-  // elements and the element build's outputs (none of them a buffer run_build carves itself)
-  DevBuf rv_in, rv_store, rv_ws, rv_el, rv_elout, rv_eloutb;
-};
 
 // Host inputs (keys, value offsets, values of kh_trie_root / kh_trie_root_nodes /
 // kh_trie_open_host) streamed to HBM behind the build instead of before it: the library's
@@ -2019,58 +1828,7 @@ struct HostStage {
   ~HostStage() { join(); }  // the stager must be done with the staging buffers before the call returns
 };
 
-// ---------------------------------------------------------------------------
-// the build
-// ---------------------------------------------------------------------------
-struct BuildArgs {
-  const uint8_t* keys;
-  uint32_t klen;
-  const uint8_t* vals;
-  const uint64_t* voff;  // [n+1] offsets, or with vlen: [n] offsets of spans anywhere in vals
-  uint64_t n;
-  const uint32_t* seg;  // nullable
-  uint64_t nseg;
-  uint32_t depth0;
-  uint32_t flags;
-  bool emit;
-  const uint32_t* vlen = nullptr;  // per-input value lengths (element builds: spans in a value heap)
-  const uint8_t* kn = nullptr;     // variable-length keys (zero-padded to 32 B): nibble counts (list tries)
-  struct ElemArgs* el = nullptr;   // element build of a resident forest commit (forest.h; nullable)
-  hipEvent_t vals_ready = nullptr; // the values / offsets land later (multi-GPU exchange): wait before reading them
-  bool dev_results = false;        // results and counters stay on the device (no host sync at the end)
-  bool no_spec = false;            // no speculative sort (SortIO::speculate): the retry of one that failed
-  std::function<void()> before_leaves;  // element builds: called (host) right before the leaves are encoded
-  std::function<bool()> late_ready;     // ... late values (ElemArgs::late) already on the device: one leaf pass
-  HostStage* hs = nullptr;  // host inputs still streaming in (keys in parts, values last; vals_ready unset)
-};
-// element build (forest.h): inputs are leaves and subtree elements; the capped reference
-// of every element node, branch and extension is kept for the forest's records
-struct ElemArgs {
-  const uint8_t* db;     // [n] EL_LEAF or subtree branch depth (input order)
-  const uint64_t* bref;  // [n*4]
-  const uint8_t* brl;    // [n]
-  const uint8_t* oldd;   // [n] previous anchor depth (EL_NEW: none)
-  const uint64_t* cref;  // [n*4] previous capped reference
-  const uint8_t* crl;    // [n]
-  // [n] nullable: the element's value arrives late (kh_block_commit: an account body that gets
-  // its storage root): the other leaves are encoded and hashed before before_leaves
-  const uint8_t* late = nullptr;
-  DevBuf* out;           // sorted el_db / el_bref / el_brl and lf_ref / lf_rlen (sized by m)
-  DevBuf* outb;          // br_ref / br_rlen, ex_ref / ex_rlen (sized by B)
-};
-struct BuildOut {
-  std::vector<uint64_t> res_hash;  // nres*4
-  std::vector<uint32_t> res_len;
-  std::vector<uint64_t> res_inl;
-};
-
 constexpr uint32_t CK_KEY_BITS = 12;  // segmented ck path: fewest key bits left in the 32-bit sort word
-static uint32_t bits_for(uint64_t nseg) {
-  uint32_t b = 0;
-  while (b < 64 && (1ULL << b) < nseg) ++b;
-  return b;
-}
-
 // the context's pinned result staging, grown to at least `bytes` (the device is drained
 // first: an earlier copy into the old buffer may still be in flight)
 static uint8_t* pinned_stage(kh_ctx* c, size_t bytes) {
@@ -2088,66 +1846,7 @@ static uint8_t* pinned_stage(kh_ctx* c, size_t bytes) {
 // a speculative sort (SortIO::speculate) met repeated keys or a long run: the build is redone
 struct SpecRetry {};
 
-static float ev_ms(hipEvent_t a, hipEvent_t b) {
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0;
-  return ms;
-}
-
-// Sort n 32-byte keys (with optional segment ids) and drop duplicates, keeping the
-// last of equal keys.  Outputs the sorted keys, the input index of each and m.
-struct SortIO {
-  const uint64_t* K32;
-  const uint32_t* seg;
-  uint32_t sb;
-  uint64_t n;
-  uint64_t *ck0, *ck1;
-  uint32_t *idx0, *idx1;
-  uint64_t* skey;
-  uint32_t* sseg;
-  void* rs_scratch;
-  void* scan_scratch;
-  unsigned long long* ctr;
-  const uint8_t* kn;  // variable-length keys: nibble counts (input order; nullable)
-  bool ck_ready = false;  // ck_path: ck0/idx0 already hold the 32-bit sort keys (k_hash_keys_ck)
-  bool ck_path = false;   // unsegmented plain build: sort (32-bit prefix, idx) only, never gather the keys
-  bool ck_made = false;   // composite path: ck0 / idx0 and the radix header already made (k_f_keys_ck)
-  // 64-bit composite path: the radix range is bits [rs_lo, 64) -- 40 (the leading 24 bits) where
-  // keys are few per segment, the tie kernel then orders the runs of equal leading 24 bits
-  int rs_lo = 32;
-  // ck path: the words are sorted on their bits from tsh up (8: hashed keys, few enough that
-  // runs of equal top-24 bits stay rare; the tie kernel orders them)
-  uint32_t tsh = 0;
-  // a device word copied to the host with the first sync's flags (c->h_pinned[1]): the
-  // caller's check of earlier stream work, read without a sync of its own (nullable)
-  const unsigned long long* chk = nullptr;
-  // ck_path: no sync for the tie kernel's flags: the sort proceeds as if no key repeats and no
-  // run is too long (hashed keys: the rule); the caller reads the flags at its next sync
-  // (CTR_TIE) and redoes the build without speculating if either is set
-  bool speculate = false;
-  // out
-  uint8_t* u = nullptr;  // ck_path: boundary values, written for the tie runs' inner boundaries
-  uint32_t depth0 = 0;
-  const uint32_t* sck = nullptr;  // ck_path: the sorted 32-bit key prefixes (skey not gathered)
-  bool ties_u = false;            // u holds the tie runs' boundaries (k_lcp skips them)
-  bool all_u = false;             // u holds every boundary (k_lcp only clears a too-long run's)
-  uint64_t m;
-  uint32_t* sidx;
-  bool fallback;
-  // Declares the sort's scratch into the caller's workspace: nk keys and their indices, skey of
-  // skey_words words, sseg for a segmented sort, the radix and scan scratch for radix_n and
-  // scan_n entries, and ctr_n counters (0: ctr is part of the caller's own counter block)
-  void declare(Layout& L, uint64_t nk, uint64_t skey_words, bool segmented, uint64_t radix_n, uint64_t scan_n,
-               uint64_t ctr_n) {
-    L.add_all(nk, ck0, ck1, idx0, idx1);
-    L.add(skey, skey_words);
-    L.add(sseg, nk, segmented);
-    L.add(rs_scratch, radix_scratch_bytes(radix_n));
-    L.add(scan_scratch, scan_scratch_bytes(scan_n, 8));
-    if (ctr_n) L.add(ctr, ctr_n);
-  }
-};
-static void sort_dedup(kh_ctx* c, SortIO& S) {
+void khst::sort_dedup(kh_ctx* c, SortIO& S) {
   hipStream_t st = c->st;
   if (S.chk && (S.ck_path || S.speculate)) throw KhError{KH_EINTERNAL, "sort: a check word on a speculative sort"};
   const uint64_t n = S.n;
@@ -2352,7 +2051,7 @@ static void sort_dedup(kh_ctx* c, SortIO& S) {
 
 static void build_stats(kh_ctx* c, const unsigned long long* hc, kh_stats* stats);
 static void run_build_once(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats* stats);
-static void run_build(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats* stats) {
+void khst::run_build(kh_ctx* c, const BuildArgs& A, BuildOut& O, kh_stats* stats) {
   try {
     run_build_once(c, A, O, stats);
   } catch (SpecRetry&) {
@@ -3021,7 +2720,7 @@ static void build_stats_sums(kh_ctx* c, const unsigned long long* sums, kh_stats
 // kec256 of n raw keys of klen bytes into K (KH_HASH_KEYS; one Keccak block up to 135 bytes).  It
 // stands below the build, and run_build_once keeps this dispatch written out: a kernel template is
 // emitted where its first host-side use stands, and the unit's code placement is measured.
-static void hash_keys_to(hipStream_t st, const uint8_t* keys, uint32_t klen, uint64_t n, uint64_t* K) {
+void khst::hash_keys_to(hipStream_t st, const uint8_t* keys, uint32_t klen, uint64_t n, uint64_t* K) {
   if (klen <= 135)
     hipLaunchKernelGGL(k_hash_keys<true>, GRID(n, BS), dim3(BS), 0, st, keys, klen, n, K);
   else
@@ -3060,30 +2759,18 @@ static kh_ctx* ctx_new(int dev) {
   return c;
 }
 
-static kh_ctx* shared_ctx(int dev) {
+kh_ctx* khst::shared_ctx(int dev) {
   std::lock_guard<std::mutex> g(g_ctx_mu);
   if ((int)g_ctx.size() <= dev) g_ctx.resize(dev + 1, nullptr);
   if (!g_ctx[dev]) g_ctx[dev] = ctx_new(dev);
   return g_ctx[dev];
 }
 
-static int current_device() {
+int khst::current_device() {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess) return 0;
   return d;
 }
-
-#define API_TRY(...)                                                    \
-  try {                                                                 \
-    __VA_ARGS__;                                                        \
-    return KH_OK;                                                       \
-  } catch (KhError & e) {                                               \
-    return set_err(e.code, e.msg);                                      \
-  } catch (std::bad_alloc&) {                                           \
-    return set_err(KH_ENOMEM, "host allocation failed");                \
-  } catch (std::exception & e) {                                        \
-    return set_err(KH_EINTERNAL, e.what());                             \
-  }
 
 // copy host inputs into the context's staging buffers
 struct Staged {
@@ -3095,7 +2782,7 @@ struct Staged {
 // Packed host bytes data[off[0], off[n]) and their n + 1 offsets, rebased to zero, into the
 // context's in_vals / in_voff on its stream.  Nothing is checked and nothing waited for: `rel` is
 // what the second copy reads, so it lives until the caller's sync.
-static void stage_packed(kh_ctx* c, const uint8_t* data, const uint64_t* off, uint64_t n, std::vector<uint64_t>& rel) {
+void khst::stage_packed(kh_ctx* c, const uint8_t* data, const uint64_t* off, uint64_t n, std::vector<uint64_t>& rel) {
   const uint64_t o0 = n ? off[0] : 0, bytes = n ? off[n] - o0 : 0;
   c->in_vals.ensure(bytes + 64);
   c->in_voff.ensure((n + 1) * 8 + 64);
@@ -3865,106 +3552,14 @@ __global__ void __launch_bounds__(BS) k_inject_roots(uint8_t* vals, const uint64
   for (int q = 0; q < 32; ++q) vals[e - 65 + q] = rb[q];
 }
 
-// ---- versioned commits (Ledger.executeBlock flushes a parallel attempt and, when
-// its root does not validate, re-executes sequentially from the SAME parent state,
-// Ledger.scala:237-271; validateBlockAfterExecution rejects a block, :603-620; TrieAccounts.rootHash
-// flushes a COPY, TrieAccounts.scala:73-80).  A savepoint opens an undo journal: every commit
-// after it saves the records it rewrites in place and logs the anchor-map slots it changes, so a
-// rollback restores the version of the savepoint in O(changed records), not O(resident trie).
-// New records, heap bytes and node ids are appended past the savepoint's ends and simply cut off.
-struct JSeg {  // one journaled commit: its saved records and map-slot log ranges (entries)
-  uint64_t rpos = 0, rn = 0;  // saved records [rpos, rpos + rn) of jidx / jrec
-  uint64_t dpos = 0, dn = 0;  // map log: the deletes (tombstones) ...
-  uint64_t ipos = 0, in = 0;  // ... and the inserts, 3 words per entry (slot, old tag, old record)
-};
-struct Savepoint {
-  uint64_t rn = 0, heap_n = 0, nleaves = 0, mused = 0, rdead = 0, map_epoch = 0, nstubs = 0;
-  uint8_t root[32] = {};
-  std::vector<uint32_t> tries;  // the last commit's touched tries and roots (kh_forest_last_roots)
-  std::vector<uint8_t> roots;
-  size_t seg0 = 0;              // journal fill at the savepoint
-  uint64_t jrec0 = 0, jmap0 = 0;
-  bool em_saved = false;        // the write-back set of the savepoint's version, kept when a later
-  bool em_valid = false;        // commit replaced it (kh_trie_emit_nodes after a rollback)
-  DevBuf em;
-  uint64_t em_n = 0, em_bytes = 0;
-};
 static void swap_buf(DevBuf& a, DevBuf& b) {
   std::swap(a.p, b.p);
   std::swap(a.cap, b.cap);
   std::swap(a.dev, b.dev);
 }
 
-struct kh_trie {
-  kh_ctx* c = nullptr;     // the context its commits run on (kh_block_commit moves the storage phase for a call)
-  kh_ctx* home = nullptr;  // the context it was opened on
-  // Handles opened through the host entry points (the shared context: the JVM's tries) run on a
-  // private context of their own (priv: streams and workspaces) and serialise on their own
-  // mutex, so commits on different handles overlap on the GPU (TxProcessor.scala:28-35 drives
-  // tries from many workers; SURVEY §8b: each handle its own HIP stream).  Handles opened on a
-  // caller's context run on it and hold its mutex (the caller owns that stream's ordering).
-  std::recursive_mutex own_mu;
-  std::recursive_mutex* lk = nullptr;  // every call on the handle holds *lk
-  kh_ctx* priv = nullptr;
-  uint32_t flags = 0;  // KH_HASH_KEYS: the trie's key encoder; KH_EMIT_NODES: keep each commit's write-back set
-  bool forest = false;
-  uint32_t tid_bits = 0;  // forests: bits of the trie ids committed so far (+ headroom; 0: none yet)
-  uint32_t lo24_off = 0;  // commits left without the 24-bit op sort (a run past the tie kernel fell back)
-  DevBuf recs, touched, replaced;  // node records (forest.h Recs: 128 B each), per-commit flags
-  uint64_t rcap = 0, rn = 0, rdead = 0;
-  DevBuf mslots;  // anchor map: 16-byte (tag, record) slots
-  uint64_t mcap = 0, mused = 0;
-  DevBuf heap;
-  uint64_t heap_n = 0;
-  uint64_t nleaves = 0;
-  // a partial handle (forest.h EL_STUB): its live stubs, and the (trie id, hash to fetch) pairs of
-  // the last commit if it was refused with KH_ENODE (kh_trie_missing)
-  uint64_t nstubs = 0;
-  std::vector<uint32_t> miss_tries;
-  std::vector<uint8_t> miss_hashes;
-  uint8_t root[32] = {};
-  DevBuf ws, elout, eloutb, em;  // commit scratch, element-build outputs, last write-back set
-  DevBuf tlb, ebuf, tbuf, ubuf, selb, merr;  // touched list, elements, trie ids + roots, upsert offsets, selections
-  DevBuf gbuf;                                // batched get: keys, records, lengths, scan scratch
-  DevBuf xbuf;                                // node export / nodes by hash: the emitted set (hashes | rlp | off)
-  uint64_t epoch = 1;  // commits, rollbacks and compactions so far (+ 1): what a kh_export_cursor is bound to
-  uint64_t em_n = 0, em_bytes = 0;
-  bool em_valid = false;
-  uint64_t ntl_hint = 0;  // touched records of the last commit (sizes the next element buffer)
-  std::vector<uint32_t> tries;  // last commit: touched tries and their roots
-  std::vector<uint8_t> roots;
-  uint32_t* d_tries = nullptr;  // ... the same on the device (in tbuf; the block commit's injection reads them)
-  uint64_t* d_roots = nullptr;
-  // versioned commits: open savepoints (innermost last) and the journal of the commits since the
-  // outermost one
-  std::vector<std::unique_ptr<Savepoint>> sps;
-  std::vector<JSeg> jsegs;
-  DevBuf jidx, jrec, jmap;  // saved record ids (u32), saved records (128 B), map-slot log (3 u64)
-  uint64_t jrec_n = 0, jmap_n = 0;
-  uint64_t map_epoch = 0;   // anchor-map rebuilds so far (a rebuild voids the slot log)
-  bool flags_dirty = false; // a descent marked records and its commit did not finish
-  DevBuf em_spare;          // the write-back buffer a savepoint's saved set rotates with
-  // a commit's tail left in flight (forest_commit, no write-back set): its records and anchor
-  // map are written after the call returned; pend (pinned) gets the map's error flag and fresh
-  // slot count, read by trie_settle before the host next needs them
-  hipEvent_t ev_roots = nullptr, pend_ev = nullptr;
-  unsigned long long* pend = nullptr;
-  bool pend_valid = false, pend_fresh = false;
-  // such a tail failed (its anchor map is not trustworthy): every later call refuses the
-  // handle (KH_EINTERNAL) except kh_trie_free
-  bool broken = false;
-  kh_trie() = default;
-  kh_trie(const kh_trie&) = delete;
-  kh_trie& operator=(const kh_trie&) = delete;
-  ~kh_trie() {
-    if (ev_roots) (void)hipEventDestroy(ev_roots);
-    if (pend_ev) (void)hipEventDestroy(pend_ev);
-    if (pend) (void)hipHostFree(pend);
-    if (priv) (void)kh_ctx_destroy(priv);
-  }
-};
 // the in-flight tail of the last commit: its map error and fresh slots (before mused is read)
-static void trie_settle(kh_trie* h) {
+void khst::trie_settle(kh_trie* h) {
   if (h->broken) throw KhError{KH_EINTERNAL, "handle unusable: an earlier commit's anchor-map update failed"};
   if (!h->pend_valid) return;
   const hipError_t e = hipEventSynchronize(h->pend_ev);
@@ -3978,8 +3573,6 @@ static void trie_settle(kh_trie* h) {
   if (h->pend_fresh) h->mused += h->pend[1];
 }
 
-// every entry point on a resident handle serialises on its home context (khst.h: reentrant)
-#define HANDLE_LOCK(h) std::lock_guard<std::recursive_mutex> handle_lock_(*(h)->lk)
 // both handles of a block commit: one mutex when they share a context, else both (std::lock:
 // no deadlock against another call locking them in the other order)
 struct PairLock {
@@ -3992,13 +3585,8 @@ struct PairLock {
   }
 };
 
-static Recs recs_of(kh_trie* h) {
-  return recs_at((uint8_t*)h->recs.p);
-}
-static AMap map_of(kh_trie* h) { return AMap{{(uint8_t*)h->mslots.p}, {(uint8_t*)h->mslots.p}, h->mcap - 1}; }
-
 // grow a device array, keeping its first `keep` bytes
-static void regrow(DevBuf& b, size_t keep, size_t bytes, hipStream_t st) {
+void khst::regrow(DevBuf& b, size_t keep, size_t bytes, hipStream_t st) {
   if (bytes <= b.cap) return;
   DevBuf nb;
   nb.ensure(bytes);
@@ -4010,7 +3598,7 @@ static void regrow(DevBuf& b, size_t keep, size_t bytes, hipStream_t st) {
   nb.p = nullptr;
   nb.cap = 0;
 }
-static void recs_reserve(kh_trie* h, uint64_t need) {
+void khst::recs_reserve(kh_trie* h, uint64_t need) {
   if (need <= h->rcap) return;
   hipStream_t st = h->c->st;
   const uint64_t cap = std::max<uint64_t>(need + need / 2, 4096), n = h->rn;
@@ -4036,7 +3624,7 @@ __global__ void __launch_bounds__(BS) k_heap_live(Recs R, uint64_t n, unsigned l
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(cnt, v);
 }
 // (re)build the anchor map with capacity >= 2 * (records + headroom), inserting every live record
-static void map_rebuild(kh_trie* h, uint64_t headroom) {
+void khst::map_rebuild(kh_trie* h, uint64_t headroom) {
   h->pend_valid = false;  // (the rebuild counts the table afresh; the stream has run the tail by its sync)
   hipStream_t st = h->c->st;
   uint64_t cap = 1024;
@@ -4130,7 +3718,7 @@ static void em_save(kh_trie* h) {
   swap_buf(h->em, h->em_spare);
 }
 // journal room for one more commit: nrec saved records, nmap map-log entries
-static JSeg journal_reserve(kh_trie* h, uint64_t nrec, uint64_t nmap) {
+JSeg khst::journal_reserve(kh_trie* h, uint64_t nrec, uint64_t nmap) {
   hipStream_t st = h->c->st;
   JSeg s;
   s.rpos = h->jrec_n;
@@ -4801,7 +4389,6 @@ struct Txn {
 };
 // MerklePatriciaTrie.copy (MerklePatriciaTrie.scala:556): an independent handle holding the
 // current version (records, anchor map, value heap, last roots and write-back set) in HBM
-static void make_private(kh_trie* h);
 static kh_trie* trie_copy(kh_trie* h) {
   trie_settle(h);
   std::unique_ptr<kh_trie> n(new kh_trie());
@@ -5196,18 +4783,9 @@ int kh_dev_list_roots(kh_ctx* c, const uint8_t* d_items, const uint64_t* d_off, 
 
 // Emission of the node set of the build just run on c (c->T): every node reachable from
 // the root whose encoding is >= 32 B, plus the root node (MerklePatriciaTrie.scala:505-511),
-// restricted to T.emit_sel when set.  Device output in `out`: hashes | rlp | off.
-struct EmitLayout {
-  uint8_t* hashes;
-  uint8_t* rlp;
-  uint64_t* off;
-};
-static EmitLayout emit_layout(DevBuf& out, uint64_t tn, uint64_t tb) {
-  uint8_t* oh = (uint8_t*)out.p;
-  uint8_t* orlp = oh + ((tn * 32 + 255) & ~255ULL);
-  uint64_t* ooff = (uint64_t*)(orlp + ((tb + 255) & ~255ULL));
-  return EmitLayout{oh, orlp, ooff};
-}
+// restricted to T.emit_sel when set.  Device output in `out`: hashes | rlp | off (host.h
+// EmitLayout).
+//
 // nodes that are not nodes of the element build appended to a write-back set (the value-only
 // branches a commit made): hashes (device, 4 words each), encodings in src at the (offset,
 // length) pairs of list (host)
@@ -5746,7 +5324,7 @@ int kh_verify_nodes_packed(const uint8_t* data, const uint64_t* off, uint64_t n,
   })
 }
 
-static kh_trie* trie_new(kh_ctx* c, uint32_t flags, bool forest) {
+extern "C++" kh_trie* khst::trie_new(kh_ctx* c, uint32_t flags, bool forest) {
   kh_trie* h = new kh_trie();
   h->c = c;
   h->home = c;
@@ -5759,7 +5337,7 @@ static kh_trie* trie_new(kh_ctx* c, uint32_t flags, bool forest) {
 // a handle of the shared context moves to a private one (kh_trie::priv) once its open has
 // completed on the shared context (its in-flight tail drained first: the private streams are
 // not ordered after the shared one)
-static void make_private(kh_trie* h) {
+extern "C++" void khst::make_private(kh_trie* h) {
   if (h->priv) return;
   trie_settle(h);
   HIPCHK(hipStreamSynchronize(h->c->st));
@@ -6290,7 +5868,7 @@ __global__ void __launch_bounds__(BS) k_get_copy(Recs R, const uint8_t* heap, co
 }
 
 // what every batch of n queries must pass (hash: the keys are raw, hashed as a commit hashes them)
-static void query_check(const kh_trie* h, const uint32_t* trie, uint32_t klen, uint64_t n, bool hash) {
+extern "C++" void khst::query_check(const kh_trie* h, const uint32_t* trie, uint32_t klen, uint64_t n, bool hash) {
   if (h->forest && n && !trie) throw KhError{KH_EINVAL, "forest queries need trie ids"};
   if (!hash && klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
   if (klen == 0 || klen > 4096) throw KhError{KH_EINVAL, "bad key length"};
@@ -6298,8 +5876,8 @@ static void query_check(const kh_trie* h, const uint32_t* trie, uint32_t klen, u
 }
 // n host query keys and their trie ids (nullable) placed in the context's in_keys and copied there
 // on its stream
-static void stage_query_keys(kh_ctx* c, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
-                             uint8_t*& dk, uint32_t*& dt) {
+extern "C++" void khst::stage_query_keys(kh_ctx* c, const uint32_t* trie, const uint8_t* keys, uint32_t klen,
+                                         uint64_t n, uint8_t*& dk, uint32_t*& dt) {
   Layout Lk;
   Lk.add(dk, n * klen + 64);
   Lk.add(dt, n, trie != nullptr);
@@ -6402,1496 +5980,8 @@ int kh_trie_get_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint
   })
 }
 
-}  // extern "C"
-
-// ---- node export and nodes by hash (export.h; the kernels are csrc/export_kernels.hip's)
-__global__ void k_export_sizes(AMap M, Recs R, const uint8_t* heap, const uint64_t* list, uint64_t r0, uint64_t n,
-                               uint32_t filter, uint32_t* stash, uint32_t* cnt, uint32_t* bytes);
-__global__ void k_export_fit(const uint32_t* cpos, const uint32_t* bpos, uint64_t n, const uint32_t* totn,
-                             const uint32_t* totb, uint64_t node_cap, uint64_t rlp_cap, unsigned long long* fit);
-__global__ void k_export_write(Recs R, const uint8_t* heap, const uint64_t* list, uint64_t r0, uint64_t n,
-                               uint32_t filter, const uint32_t* stash, const uint32_t* cpos, const uint32_t* bpos,
-                               uint8_t* hashes, uint8_t* rlp, uint64_t* off, uint8_t* found, const uint64_t* bpos64);
-__global__ void k_export_verify(const uint8_t* hashes, const uint8_t* rlp, const uint64_t* off, uint64_t n,
-                                unsigned long long* bad);
-__global__ void k_by_hash_scan(Recs R, uint64_t rn, const uint64_t* Q, uint32_t nq, uint64_t* hits);
-
-// records sized per pass: the child stash is 64 B a record (64 MiB), and two nodes of <= 532 B a
-// record keep the 32-bit scans of a pass far from overflow
-constexpr uint64_t EXPORT_WINDOW = 1ULL << 20;
-constexpr uint64_t BYHASH_MAX = 4096, BYHASH_PASS = 2048;  // queries a call / an LDS table takes
-
-static int trie_export(kh_trie* h, uint32_t filter, uint32_t flags, kh_export_cursor* cur, uint8_t* hashes32,
-                       uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off, uint64_t* n_nodes,
-                       uint64_t* rlp_len, int* done) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  const bool fresh = cur->next == 0 && cur->epoch == 0;  // a zeroed cursor starts here
-  if ((!fresh && cur->epoch != h->epoch) || cur->next > h->rn)
-    throw KhError{KH_EINVAL, "export cursor from before a commit, rollback or compaction of the handle"};
-  uint64_t next = cur->next, wn = 0, wb = 0, need_n = 0, need_b = 0;
-  bool short_out = false;
-  while (next < h->rn && !short_out) {
-    const uint64_t W = std::min(h->rn - next, EXPORT_WINDOW);
-    Layout L;
-    uint32_t *cnt, *byt, *stash, *tot;
-    unsigned long long* fit;
-    char* scr;
-    L.add(cnt, W + 1);
-    L.add(byt, W + 1);
-    L.add(stash, W * EXP_LANES);
-    L.add(scr, scan_scratch_bytes(W + 1, 4));
-    L.add(tot, 4);
-    L.add(fit, 8);  // [0..4] k_export_fit, [5] the verify counter
-    place(h->gbuf, L);
-    const Recs R = recs_of(h);
-    const uint8_t* heap = (const uint8_t*)h->heap.p;
-    HIPCHK(hipMemsetAsync(fit, 0, 64, st));
-    hipLaunchKernelGGL(k_export_sizes, GRID(W * EXP_LANES, BS), dim3(BS), 0, st, map_of(h), R, heap,
-                       (const uint64_t*)nullptr, next, W, filter, stash, cnt, byt);
-    LAUNCH_CHECK();
-    scan_exclusive<uint32_t>(cnt, cnt, W, tot, scr, st);
-    scan_exclusive<uint32_t>(byt, byt, W, tot + 1, scr, st);
-    hipLaunchKernelGGL(k_export_fit, GRID(W + 1, BS), dim3(BS), 0, st, (const uint32_t*)cnt, (const uint32_t*)byt, W,
-                       (const uint32_t*)tot, (const uint32_t*)(tot + 1), node_cap - wn, rlp_cap - wb, fit);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, fit, 40, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t k = c->h_pinned[0], tn = c->h_pinned[1], tb = c->h_pinned[2];
-    if (k > W || wn + tn > node_cap || wb + tb > rlp_cap) throw KhError{KH_EINTERNAL, "export: bad prefix"};
-    if (k < W) {  // record next + k does not fit what is left
-      short_out = true;
-      need_n = c->h_pinned[3];
-      need_b = c->h_pinned[4];
-    }
-    if (tn) {
-      h->xbuf.ensure(tn * 32 + tb + (tn + 1) * 8 + 1024);
-      const EmitLayout E = emit_layout(h->xbuf, tn, tb);
-      hipLaunchKernelGGL(k_export_write, GRID(k * EXP_LANES, BS), dim3(BS), 0, st, R, heap, (const uint64_t*)nullptr,
-                         next, k, filter, (const uint32_t*)stash, (const uint32_t*)cnt, (const uint32_t*)byt, E.hashes,
-                         E.rlp, E.off, (uint8_t*)nullptr, (const uint64_t*)nullptr);
-      LAUNCH_CHECK();
-      c->h_pinned[8] = tb;
-      HIPCHK(hipMemcpyAsync(E.off + tn, c->h_pinned + 8, 8, hipMemcpyHostToDevice, st));
-      if (flags & KH_EXPORT_VERIFY) {
-        hipLaunchKernelGGL(k_export_verify, GRID(tn, BS), dim3(BS), 0, st, (const uint8_t*)E.hashes,
-                           (const uint8_t*)E.rlp, (const uint64_t*)E.off, tn, fit + 5);
-        LAUNCH_CHECK();
-        HIPCHK(hipMemcpyAsync(c->h_pinned + 9, fit + 5, 8, hipMemcpyDeviceToHost, st));
-      }
-      HIPCHK(hipMemcpyAsync(hashes32 + 32 * wn, E.hashes, tn * 32, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(rlp + wb, E.rlp, tb, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(off + wn, E.off, tn * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if ((flags & KH_EXPORT_VERIFY) && c->h_pinned[9])
-        throw KhError{KH_EINTERNAL, "export verify: a re-encoded node does not hash to its cached reference"};
-      for (uint64_t j = 0; j < tn; ++j) off[wn + j] += wb;
-    }
-    wn += tn;
-    wb += tb;
-    next += k;
-  }
-  if (wn == 0 && short_out) {  // not even the next record's nodes fit: the cursor stays
-    *n_nodes = need_n;
-    *rlp_len = need_b;
-    return set_err(KH_ENOSPC, "output too small for the next record (*n_nodes / *rlp_len hold what it needs)");
-  }
-  if (off) off[wn] = wb;
-  *n_nodes = wn;
-  *rlp_len = wb;
-  cur->next = next;
-  cur->epoch = h->epoch;
-  *done = next >= h->rn;
-  return KH_OK;
-}
-
-static int trie_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8_t* found, uint8_t* rlp,
-                        uint64_t rlp_cap, uint64_t* off, uint64_t* rlp_len) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  Layout L;
-  uint64_t *Q, *hits;
-  uint32_t *byt, *stash, *tot;
-  uint8_t* fnd;
-  char* scr;
-  L.add(Q, n * 4);
-  L.add(hits, n);
-  L.add(byt, n + 1);
-  L.add(stash, n * EXP_LANES);
-  L.add(fnd, n);
-  L.add(scr, scan_scratch_bytes(n + 1, 4));
-  L.add(tot, 4);
-  place(h->gbuf, L);
-  const Recs R = recs_of(h);
-  const uint8_t* heap = (const uint8_t*)h->heap.p;
-  HIPCHK(hipMemcpyAsync(Q, hashes32, n * 32, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(hits, 0xFF, n * 8, st));
-  if (h->rn && h->mcap) {
-    const uint64_t blocks = std::min<uint64_t>((h->rn + BS - 1) / BS, 1024);  // (4 blocks a CU, grid-stride)
-    for (uint64_t q0 = 0; q0 < n; q0 += BYHASH_PASS) {
-      hipLaunchKernelGGL(k_by_hash_scan, dim3((unsigned)blocks), dim3(BS), 0, st, R, h->rn, (const uint64_t*)Q + 4 * q0,
-                         (uint32_t)std::min(n - q0, BYHASH_PASS), hits + q0);
-      LAUNCH_CHECK();
-    }
-  }
-  hipLaunchKernelGGL(k_export_sizes, GRID(n * EXP_LANES, BS), dim3(BS), 0, st, map_of(h), R, heap, (const uint64_t*)hits,
-                     (uint64_t)0, n, EXP_ALL_TRIES, stash, (uint32_t*)nullptr, byt);
-  LAUNCH_CHECK();
-  scan_exclusive<uint32_t>(byt, byt, n, tot, scr, st);
-  HIPCHK(hipMemcpyAsync(byt + n, tot, 4, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t total = (uint32_t)c->h_pinned[0];
-  *rlp_len = total;
-  if (total > rlp_cap || (total && !rlp))
-    return set_err(KH_ENOSPC, "encoding output too small (*rlp_len holds the size needed)");
-  h->xbuf.ensure(total + 1024);
-  hipLaunchKernelGGL(k_export_write, GRID(n * EXP_LANES, BS), dim3(BS), 0, st, R, heap, (const uint64_t*)hits,
-                     (uint64_t)0, n, EXP_ALL_TRIES, (const uint32_t*)stash, (const uint32_t*)nullptr,
-                     (const uint32_t*)byt, (uint8_t*)nullptr, (uint8_t*)h->xbuf.p, (uint64_t*)nullptr, fnd,
-                     (const uint64_t*)nullptr);
-  LAUNCH_CHECK();
-  std::vector<uint32_t> o32(n + 1);
-  HIPCHK(hipMemcpyAsync(o32.data(), byt, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(found, fnd, n, hipMemcpyDeviceToHost, st));
-  if (total) HIPCHK(hipMemcpyAsync(rlp, h->xbuf.p, total, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i <= n; ++i) off[i] = o32[i];
-  return KH_OK;
-}
-
-// ---- Merkle proofs (prove.h; the kernels are csrc/prove_kernels.hip's)
-__global__ void k_prove_count(AMap M, Recs R, const uint64_t* K, const uint32_t* trie, uint64_t n, uint64_t* cnt,
-                              uint8_t* found);
-__global__ void k_prove_fill(AMap M, Recs R, const uint64_t* K, const uint32_t* trie, uint64_t n, const uint64_t* pos,
-                             uint64_t* hits);
-__global__ void k_prove_iota(uint32_t* v, uint64_t n);
-__global__ void k_prove_first(const uint64_t* sorted, uint64_t n, uint32_t* first);
-__global__ void k_prove_rank(const uint64_t* sorted, const uint32_t* src, const uint32_t* first, const uint32_t* rank,
-                             uint64_t n, uint64_t* table, uint32_t* path_idx);
-__global__ void k_proof_walk(ProofTable T, const uint8_t* roots, uint64_t nroots, const uint8_t* keys,
-                             const uint32_t* path_idx, const uint64_t* path_off, uint64_t n, uint8_t* status,
-                             uint64_t* vsrc, uint64_t* vlen);
-__global__ void k_proof_copy(const uint8_t* rlp, const uint64_t* vsrc, const uint64_t* vlen, const uint64_t* voff,
-                             uint64_t n, uint8_t* out);
-
-// The proofs of n keys (host buffers).  Count walk, 64-bit scan, fill walk (the same body), for
-// KH_PROVE_SHARED a sort of the hits with an adjacent-unique pass, then the export kernels in
-// list mode over the hits.  Hit counts and encoding bytes are scanned in 64 bits: n < 2^31 keys
-// of up to 130 nodes of up to 532 B pass 2^32 either way; the listed nodes of a call are capped at
-// 2^32 - 1 (path_idx is 32 bits wide).
-static int trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n, uint32_t flags,
-                      uint8_t* found, uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap,
-                      uint64_t* off, uint32_t* path_idx, uint64_t path_cap, uint64_t* path_off, uint64_t* n_nodes,
-                      uint64_t* rlp_len, uint64_t* n_path) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  // KH_PROVE_TRIE_KEYS: the keys are trie keys already (a range scan's), never hashed
-  const bool hash = (h->flags & KH_HASH_KEYS) && !(flags & KH_PROVE_TRIE_KEYS);
-  query_check(h, trie, klen, n, hash);
-  *n_nodes = *rlp_len = *n_path = 0;
-  if (n == 0) {
-    path_off[0] = 0;
-    if (off) off[0] = 0;
-    return KH_OK;
-  }
-  const bool shared = (flags & KH_PROVE_SHARED) != 0;
-  // the keys and trie ids staged, the keys hashed as a commit hashes them
-  uint8_t* dk;
-  uint32_t* dt;
-  stage_query_keys(c, trie, keys, klen, n, dk, dt);
-  Layout L1;
-  uint64_t *K, *pos, *tot;
-  uint8_t* fnd;
-  char* scr1;
-  L1.add(K, n * 4 + 8);
-  L1.add(pos, n + 1);
-  L1.add(fnd, n);
-  L1.add(scr1, scan_scratch_bytes(n + 1, 8));
-  L1.add(tot, 8);
-  place(h->gbuf, L1);
-  if (hash) {
-    hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
-  } else {
-    HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
-  }
-  const bool any = h->rn && h->mcap;  // (else an empty trie or forest: every proof is empty)
-  const Recs R = recs_of(h);
-  const uint8_t* heap = (const uint8_t*)h->heap.p;
-  if (any) {
-    hipLaunchKernelGGL(k_prove_count, GRID(n, BS), dim3(BS), 0, st, map_of(h), R, (const uint64_t*)K,
-                       (const uint32_t*)dt, n, pos, fnd);
-    LAUNCH_CHECK();
-  } else {
-    HIPCHK(hipMemsetAsync(pos, 0, n * 8, st));
-    HIPCHK(hipMemsetAsync(fnd, 0, n, st));
-  }
-  scan_exclusive<uint64_t>(pos, pos, n, tot, scr1, st);
-  HIPCHK(hipMemcpyAsync(pos + n, tot, 8, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t np = c->h_pinned[0];
-  if (np >= (1ULL << 32)) throw KhError{KH_EINVAL, "the proofs list 2^32 nodes or more: prove fewer keys a call"};
-  // the hits in proof order, then the node table's hit list (shared: the distinct hits, sorted)
-  Layout L2;
-  uint64_t *hits, *hits2, *table;
-  uint32_t *src, *src2, *first, *rank, *pidx, *utot;
-  char *rscr, *scr2;
-  L2.add(hits, np + 1);
-  L2.add(pidx, np + 1);
-  L2.add(hits2, np + 1, shared);
-  L2.add(table, np + 1, shared);
-  L2.add(src, np + 1, shared);
-  L2.add(src2, np + 1, shared);
-  L2.add(first, np + 1, shared);
-  L2.add(rank, np + 1, shared);
-  L2.add(rscr, radix_scratch_bytes(np + 1), shared);
-  L2.add(scr2, scan_scratch_bytes(np + 1, 4), shared);
-  L2.add(utot, 4);
-  place(c->ws1, L2);
-  uint64_t nn = np;
-  const uint64_t* list = hits;
-  if (np) {
-    hipLaunchKernelGGL(k_prove_fill, GRID(n, BS), dim3(BS), 0, st, map_of(h), R, (const uint64_t*)K, (const uint32_t*)dt,
-                       n, (const uint64_t*)pos, hits);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_prove_iota, GRID(np, BS), dim3(BS), 0, st, shared ? src : pidx, np);
-    LAUNCH_CHECK();
-    if (shared) {
-      // a hit is 2 * record + which < 2^33: five 8-bit digits
-      const bool flip = radix_sort_pairs<uint64_t>(hits, src, hits2, src2, np, 0, 40, rscr, st);
-      const uint64_t* sk = flip ? hits2 : hits;
-      const uint32_t* sv = flip ? src2 : src;
-      hipLaunchKernelGGL(k_prove_first, GRID(np, BS), dim3(BS), 0, st, sk, np, first);
-      LAUNCH_CHECK();
-      scan_exclusive<uint32_t>(first, rank, np, utot, scr2, st);
-      hipLaunchKernelGGL(k_prove_rank, GRID(np, BS), dim3(BS), 0, st, sk, sv, (const uint32_t*)first,
-                         (const uint32_t*)rank, np, table, pidx);
-      LAUNCH_CHECK();
-      HIPCHK(hipMemcpyAsync(c->h_pinned, utot, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      nn = (uint32_t)c->h_pinned[0];
-      list = table;
-    }
-  }
-  // the table's encodings: sizes, 64-bit scan, write (list mode, one node an item)
-  Layout L3;
-  uint32_t *byt, *stash;
-  uint64_t* tb;
-  char* scr3;
-  L3.add(byt, nn + 1);
-  L3.add(stash, (nn + 1) * EXP_LANES);
-  L3.add(scr3, scan_scratch_bytes(nn + 1, 8));
-  L3.add(tb, 8);
-  place(c->ws2, L3);
-  // (the offsets scanned in place in the emitted set's off array, which the write pass reads)
-  h->xbuf.ensure(nn * 32 + (nn + 1) * 8 + 2048);
-  uint64_t* doff = (uint64_t*)((uint8_t*)h->xbuf.p + ((nn * 32 + 255) & ~255ULL));
-  uint64_t total = 0;
-  if (nn) {
-    hipLaunchKernelGGL(k_export_sizes, GRID(nn * EXP_LANES, BS), dim3(BS), 0, st, map_of(h), R, heap, list, (uint64_t)0,
-                       nn, EXP_ALL_TRIES, stash, (uint32_t*)nullptr, byt);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_u32_to_u64, GRID(nn, BS), dim3(BS), 0, st, (const uint32_t*)byt, nn, doff);
-    LAUNCH_CHECK();
-    scan_exclusive<uint64_t>(doff, doff, nn, tb, scr3, st);
-    HIPCHK(hipMemcpyAsync(doff + nn, tb, 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned, tb, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    total = c->h_pinned[0];
-  }
-  *n_nodes = nn;
-  *rlp_len = total;
-  *n_path = np;
-  if (nn > node_cap || total > rlp_cap || np > path_cap)
-    return set_err(KH_ENOSPC, "proof output too small (*n_nodes / *rlp_len / *n_path hold the sizes needed)");
-  if ((nn && (!hashes32 || !off)) || (total && !rlp) || (np && !path_idx))
-    throw KhError{KH_EINVAL, "null output buffer"};
-  if (nn) {
-    DevBuf& enc = c->out_emit;  // the encodings (hashes and offsets: the handle's xbuf, above)
-    enc.ensure(total + 1024);
-    hipLaunchKernelGGL(k_export_write, GRID(nn * EXP_LANES, BS), dim3(BS), 0, st, R, heap, list, (uint64_t)0, nn,
-                       EXP_ALL_TRIES, (const uint32_t*)stash, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                       (uint8_t*)h->xbuf.p, (uint8_t*)enc.p, doff, (uint8_t*)nullptr, (const uint64_t*)doff);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(hashes32, h->xbuf.p, nn * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(off, doff, (nn + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (total) HIPCHK(hipMemcpyAsync(rlp, enc.p, total, hipMemcpyDeviceToHost, st));
-  } else if (off) {
-    off[0] = 0;
-  }
-  if (np) HIPCHK(hipMemcpyAsync(path_idx, pidx, np * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(path_off, pos, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(found, fnd, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return KH_OK;
-}
-
-// The proofs of n keys checked (host buffers, the shared context): the table's nodes hashed once
-// each, one walk per key, the values packed.
-static int verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t* keys, uint32_t klen, uint64_t n,
-                         uint32_t flags, const uint8_t* rlp, const uint64_t* off, uint64_t n_nodes,
-                         const uint32_t* path_idx, const uint64_t* path_off, uint8_t* status, uint8_t* vals,
-                         uint64_t val_cap, uint64_t* voff, uint64_t* val_bytes) {
-  if (val_bytes) *val_bytes = 0;
-  if (n == 0) {
-    voff[0] = 0;
-    return KH_OK;
-  }
-  for (uint64_t j = 0; j < n_nodes; ++j) {
-    if (off[j + 1] < off[j]) throw KhError{KH_EINVAL, "node offsets must not decrease"};
-    if (off[j + 1] - off[j] > 0xFFFFFFFFull) throw KhError{KH_EINVAL, "a node longer than 2^32 - 1 bytes"};
-  }
-  for (uint64_t i = 0; i < n; ++i)
-    if (path_off[i + 1] < path_off[i]) throw KhError{KH_EINVAL, "path offsets must not decrease"};
-  const uint64_t p0 = path_off[0], np = path_off[n] - p0;
-  const uint64_t b0 = n_nodes ? off[0] : 0, nb = n_nodes ? off[n_nodes] - b0 : 0;
-  if ((np && !path_idx) || (nb && !rlp)) throw KhError{KH_EINVAL, "null buffer"};
-  kh_ctx* c = shared_ctx(current_device());
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  HIPCHK(hipSetDevice(c->dev));
-  hipStream_t st = c->st;
-  std::vector<uint64_t> roff(n_nodes + 1, 0), rpo(n + 1);
-  for (uint64_t j = 0; j <= n_nodes && n_nodes; ++j) roff[j] = off[j] - b0;
-  for (uint64_t i = 0; i <= n; ++i) rpo[i] = path_off[i] - p0;
-  Layout Li;
-  uint8_t *dk, *droots, *drlp;
-  uint64_t *doff, *dpo;
-  uint32_t* dpi;
-  Li.add(dk, n * klen + 64);
-  Li.add(droots, nroots * 32);
-  Li.add(drlp, nb + 64);
-  Li.add(doff, n_nodes + 1);
-  Li.add(dpi, np + 1);
-  Li.add(dpo, n + 1);
-  place(c->in_keys, Li);
-  HIPCHK(hipMemcpyAsync(dk, keys, n * klen, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(droots, roots32, nroots * 32, hipMemcpyHostToDevice, st));
-  if (nb) HIPCHK(hipMemcpyAsync(drlp, rlp + b0, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(doff, roff.data(), (n_nodes + 1) * 8, hipMemcpyHostToDevice, st));
-  if (np) HIPCHK(hipMemcpyAsync(dpi, path_idx + p0, np * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dpo, rpo.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-  Layout Lw;
-  uint64_t *K, *nh, *vsrc, *vlen, *dvoff, *tot;
-  uint8_t* dst;
-  char* scr;
-  Lw.add(K, n * 4 + 8);
-  Lw.add(nh, n_nodes * 4 + 4);
-  Lw.add(vsrc, n);
-  Lw.add(vlen, n + 1);
-  Lw.add(dvoff, n + 1);
-  Lw.add(dst, n);
-  Lw.add(scr, scan_scratch_bytes(n + 1, 8));
-  Lw.add(tot, 8);
-  place(c->ws1, Lw);
-  if (flags & KH_HASH_KEYS) {
-    hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
-  } else {
-    HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
-  }
-  if (n_nodes) {
-    hipLaunchKernelGGL(k_kec_batch, GRID(n_nodes, BS), dim3(BS), 0, st, (const uint8_t*)drlp, (const uint64_t*)doff,
-                       n_nodes, nh);
-    LAUNCH_CHECK();
-  }
-  const ProofTable T{drlp, doff, nh, n_nodes};
-  hipLaunchKernelGGL(k_proof_walk, GRID(n, BS), dim3(BS), 0, st, T, (const uint8_t*)droots, nroots, (const uint8_t*)K,
-                     (const uint32_t*)dpi, (const uint64_t*)dpo, n, dst, vsrc, vlen);
-  LAUNCH_CHECK();
-  scan_exclusive<uint64_t>(vlen, dvoff, n, tot, scr, st);
-  HIPCHK(hipMemcpyAsync(dvoff + n, tot, 8, hipMemcpyDeviceToDevice, st));
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t total = c->h_pinned[0];
-  if (val_bytes) *val_bytes = total;
-  if (total > val_cap || (total && !vals))
-    return set_err(KH_ENOSPC, "value output too small (*val_bytes holds the size needed)");
-  c->out_emit.ensure(total + 64);
-  if (total) {
-    hipLaunchKernelGGL(k_proof_copy, GRID(n, BS), dim3(BS), 0, st, (const uint8_t*)drlp, (const uint64_t*)vsrc,
-                       (const uint64_t*)vlen, (const uint64_t*)dvoff, n, (uint8_t*)c->out_emit.p);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(vals, c->out_emit.p, total, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(voff, dvoff, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return KH_OK;
-}
-
-// ---- forest load, roots and eviction (load.h; the kernels are csrc/load_kernels.hip's)
-__global__ void k_load_root_flags(const uint64_t* roots, uint64_t k, uint32_t* flag);
-__global__ void k_load_roots(const uint64_t* roots, uint64_t k, const uint32_t* flag, const uint32_t* pos, LItems N);
-__global__ void k_load_resident(AMap M, Recs R, const uint32_t* tries, uint64_t k, unsigned long long* n_resident);
-__global__ void k_load_count(LItems I, uint64_t ni, NStore S, LCounts C, unsigned long long* tot, int partial);
-__global__ void k_load_fill(LItems I, uint64_t ni, NStore S, LCounts C, LItems N, const uint32_t* tries, uint8_t* recs,
-                            uint64_t rbase, uint64_t rcap, uint8_t* heap, uint64_t hbase, uint64_t heap_cap,
-                            int partial);
-__global__ void k_fill_flags(Recs R, uint64_t n, NStore S, uint32_t* flag);
-__global__ void k_fill_items(Recs R, uint64_t n, const uint32_t* flag, const uint32_t* pos, LItems N, uint32_t* tries,
-                             uint32_t* list);
-__global__ void k_need(AMap M, Recs R, const uint64_t* K, const uint32_t* trie, uint64_t n, uint8_t* flag,
-                       uint64_t* hash);
-__global__ void k_load_missing(LItems I, uint64_t ni, const uint32_t* miss, const uint32_t* mpos, uint64_t cap,
-                               uint32_t* out_idx, uint64_t* out_hash);
-__global__ void k_roots_flags(Recs R, uint64_t n, uint32_t* flag);
-__global__ void k_roots_write(Recs R, uint64_t n, const uint32_t* flag, const uint32_t* pos, uint64_t cap,
-                              uint32_t* tries, uint64_t* roots);
-__global__ void k_evict_flags(Recs R, uint64_t n, const uint32_t* tries, uint32_t nt, uint32_t* flag,
-                              unsigned long long* cnt);
-__global__ void k_evict_list(uint64_t n, const uint32_t* flag, const uint32_t* pos, uint64_t cap, uint32_t* list);
-
-static LItems litems_carve(DevBuf& b, uint64_t cap) {
-  Layout L;
-  LItems I{};
-  L.add(I.pre, cap * 4);
-  L.add_all(cap, I.a, I.d);
-  L.add(I.ref, cap * 4);
-  L.add(I.rl, cap);
-  L.add(I.pref, cap * 4);
-  L.add(I.prl, cap);
-  L.add(I.j, cap);
-  place(b, L);
-  I.cap = cap;
-  return I;
-}
-
-// k tries (ids tries[j], roots roots32[32j..), host arrays) decoded from n stored node encodings
-// (device buffers) into forest h, beside what it holds.  All or nothing: a refusal or failure
-// before the anchor map is touched leaves no record past the old count (the slots cleared) and
-// every host-side field as it was.  With a savepoint open the map inserts are journaled.
-// A single trie opens the same way (open_store): trie id 0 into a fresh non-forest handle.
-//
-// mode LOAD_PARTIAL (kh_forest_load_partial, kh_trie_open_partial): a hash absent from the store
-// below a root makes a stub (forest.h EL_STUB) instead of ending the round; a missing root is
-// reported as ever.  mode LOAD_FILL (kh_trie_fill_nodes; tries, roots32, k unused): round 0 is the
-// live stubs whose missing node the store holds, in record order; the rounds append as a partial
-// load does, and only after the last one do the listed stubs leave the map and die, the new
-// records taking their anchors -- so a failure before that leaves the handle as it was.
-enum LoadMode { LOAD_FULL = 0, LOAD_PARTIAL = 1, LOAD_FILL = 2 };
-static void forest_load(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
-                        const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
-                        uint64_t* n_missing, kh_stats* stats, LoadMode mode = LOAD_FULL,
-                        uint64_t* n_decoded = nullptr) {
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  const bool fill = mode == LOAD_FILL;
-  if (fill) k = 0;
-  if (k >= (1ULL << 31) || n >= (1ULL << 31)) throw KhError{KH_EINVAL, "trie list or node store too large"};
-  if (fill && !h->sps.empty()) throw KhError{KH_EINVAL, "kh_trie_fill_nodes: a savepoint is open"};
-  if (!fill) {
-    std::vector<uint32_t> ids(tries, tries + k);
-    std::sort(ids.begin(), ids.end());
-    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
-      throw KhError{KH_EINVAL, "kh_forest_load_nodes: a trie id is listed twice"};
-  }
-  trie_settle(h);
-  if (fill ? (h->nstubs == 0 || n == 0 || h->rn == 0) : k == 0) {
-    ++h->epoch;
-    return;
-  }
-  HIPCHK(hipEventRecord(c->ev[6], st));
-  const uint64_t nscan = fill ? h->rn : 0;  // fill: the records scanned for stubs
-  // the list on the device, the roots to walk (not the empty trie's) and the resident check
-  Layout Lr;
-  uint32_t *dtries, *rflag, *rpos, *dmidx;
-  uint64_t *droots, *dmhash;
-  unsigned long long* tot;
-  char* rscr;
-  const uint64_t mcap = std::min<uint64_t>(miss_cap, 1ULL << 24);
-  const uint64_t kk = fill ? nscan : k;  // (fill: a list entry per stub found, at most one per record)
-  uint32_t* slist = nullptr;            // fill: the stubs of round 0
-  Lr.add(dtries, kk);
-  Lr.add(droots, k * 4);
-  Lr.add_all(kk, rflag, rpos);
-  Lr.add(rscr, scan_scratch_bytes(kk + 1, 4));
-  Lr.add(tot, 8);
-  Lr.add(dmidx, mcap + 1);
-  Lr.add(dmhash, (mcap + 1) * 4);
-  Lr.add(slist, nscan);
-  place(h->gbuf, Lr);
-  if (!fill) {
-    HIPCHK(hipMemcpyAsync(dtries, tries, k * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(droots, roots32, k * 32, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
-  uint64_t ni = 0;
-  uint32_t max_id = 0;
-  if (!fill) {
-    if (h->rn && h->mcap) {
-      hipLaunchKernelGGL(k_load_resident, GRID(k, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint32_t*)dtries,
-                         k, tot + 6);
-      LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_load_root_flags, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k, rflag);
-    LAUNCH_CHECK();
-    scan_exclusive<uint32_t>(rflag, rpos, k, (uint32_t*)tot, rscr, st);
-    HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (c->h_pinned[6]) throw KhError{KH_EINVAL, "kh_forest_load_nodes: a listed trie is already resident"};
-    ni = (uint32_t)c->h_pinned[0];
-    for (uint64_t j = 0; j < k; ++j) max_id = std::max(max_id, tries[j]);
-    if (ni == 0) {  // every root is the empty trie's
-      ++h->epoch;
-      return;
-    }
-  }
-  // the store, keyed by kec256 of each encoding (content addressed)
-  Layout L;
-  uint64_t* hs;
-  SortIO S{};
-  L.add(hs, n * 4 + 4);
-  S.declare(L, n, n * 4 + 4, false, n + 1, n + 1, CTR_N);
-  place(h->ws, L);
-  S.K32 = hs;
-  S.n = n;
-  HIPCHK(hipMemsetAsync(S.ctr, 0, CTR_N * 8, st));
-  NStore NS{nullptr, nullptr, 0, d_enc, d_off};
-  if (n) {
-    hipLaunchKernelGGL(k_kec_batch, GRID(n, BS), dim3(BS), 0, st, d_enc, d_off, n, hs);
-    LAUNCH_CHECK();
-    sort_dedup(c, S);
-    NS.hash = S.skey;
-    NS.idx = S.sidx;
-    NS.m = S.m;
-  }
-  HIPCHK(hipEventRecord(c->ev[0], st));  // (stats: the store is hashed and sorted)
-  const uint64_t rn0 = h->rn;
-  uint64_t heap_cur = h->heap_n, keys = 0, stubs_made = 0, decoded = 0, nfilled = 0;
-  uint32_t rounds = 0;
-  bool map_stage = false;
-  try {
-    DevBuf fa, fb, cb;
-    LItems cur{};
-    if (fill) {  // round 0: the stubs the store resolves, in record order
-      hipLaunchKernelGGL(k_fill_flags, GRID(nscan, BS), dim3(BS), 0, st, recs_of(h), nscan, NS, rflag);
-      LAUNCH_CHECK();
-      scan_exclusive<uint32_t>(rflag, rpos, nscan, (uint32_t*)tot, rscr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      ni = nfilled = (uint32_t)c->h_pinned[0];
-      if (ni == 0) {  // no stub names a node of the store: nothing to do
-        ++h->epoch;
-        if (n_decoded) *n_decoded = 0;
-        return;
-      }
-      cur = litems_carve(fa, ni);
-      hipLaunchKernelGGL(k_fill_items, GRID(nscan, BS), dim3(BS), 0, st, recs_of(h), nscan, (const uint32_t*)rflag,
-                         (const uint32_t*)rpos, cur, dtries, slist);
-      LAUNCH_CHECK();
-    } else {
-      cur = litems_carve(fa, ni);
-      hipLaunchKernelGGL(k_load_roots, GRID(k, BS), dim3(BS), 0, st, (const uint64_t*)droots, k,
-                         (const uint32_t*)rflag, (const uint32_t*)rpos, cur);
-      LAUNCH_CHECK();
-    }
-    for (; ni && rounds < 80; ++rounds) {
-      // (a root is never a stub: round 0 of a partial load reports a missing root as the full load does)
-      const int partial = fill || (mode == LOAD_PARTIAL && rounds > 0);
-      // count, scans, one sync
-      Layout Lc;
-      LCounts C{};
-      uint32_t* mpos;
-      char* scr;
-      Lc.add_all(ni, C.child, C.rec);
-      Lc.add(C.val, ni);
-      Lc.add_all(ni, C.miss, C.src, mpos);
-      Lc.add(scr, scan_scratch_bytes(ni + 1, 8));
-      place(cb, Lc);
-      HIPCHK(hipMemsetAsync(tot, 0, 64, st));
-      hipLaunchKernelGGL(k_load_count, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, tot, partial);
-      LAUNCH_CHECK();
-      scan_exclusive<uint32_t>(C.child, C.child, ni, (uint32_t*)tot, scr, st);
-      scan_exclusive<uint32_t>(C.rec, C.rec, ni, (uint32_t*)(tot + 1), scr, st);
-      scan_exclusive<uint64_t>(C.val, C.val, ni, (uint64_t*)(tot + 2), scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t nchild = (uint32_t)c->h_pinned[0], nrec = (uint32_t)c->h_pinned[1], nval = c->h_pinned[2];
-      const uint64_t code = c->h_pinned[3], nmiss = c->h_pinned[4];
-      keys += c->h_pinned[5];
-      stubs_made += c->h_pinned[6];
-      decoded += c->h_pinned[7];
-      if (code == OPEN_VALUE) throw KhError{KH_EINVAL, "a branch with a value: not a secure trie"};
-      if (code) throw KhError{KH_EINVAL, "the store holds a node that is not a canonical secure-trie node"};
-      if (nmiss) {  // every missing reference of this round (MPTNodeMissingException), then stop
-        const uint64_t w = std::min(nmiss, mcap);
-        if (w) {
-          scan_exclusive<uint32_t>(C.miss, mpos, ni, (uint32_t*)(tot + 7), scr, st);
-          hipLaunchKernelGGL(k_load_missing, GRID(ni, BS), dim3(BS), 0, st, cur, ni, (const uint32_t*)C.miss,
-                             (const uint32_t*)mpos, w, dmidx, dmhash);
-          LAUNCH_CHECK();
-          HIPCHK(hipMemcpyAsync(miss_idx, dmidx, w * 4, hipMemcpyDeviceToHost, st));
-          HIPCHK(hipMemcpyAsync(miss32, dmhash, w * 32, hipMemcpyDeviceToHost, st));
-          HIPCHK(hipStreamSynchronize(st));
-        }
-        if (n_missing) *n_missing = nmiss;
-        throw KhError{KH_ENODE, "node missing from the store (MPTNodeMissingException)"};
-      }
-      if (h->rn + nrec >= (uint64_t)NONE) throw KhError{KH_EINVAL, "the load passes the forest's record limit"};
-      // fill: the records, the values and the next frontier at exactly the scanned sizes
-      recs_reserve(h, h->rn + nrec + 16);
-      const uint64_t hneed = heap_cur + nval + 64;
-      if (hneed > h->heap.cap) regrow(h->heap, heap_cur, hneed + hneed / 4, st);
-      LItems nxt = litems_carve(rounds & 1 ? fa : fb, std::max<uint64_t>(nchild, 1));
-      hipLaunchKernelGGL(k_load_fill, GRID(ni, BS), dim3(BS), 0, st, cur, ni, NS, C, nxt, (const uint32_t*)dtries,
-                         (uint8_t*)h->recs.p, h->rn, h->rcap, (uint8_t*)h->heap.p, heap_cur, (uint64_t)h->heap.cap,
-                         partial);
-      LAUNCH_CHECK();
-      h->rn += nrec;  // (a later regrow keeps the records of the earlier rounds)
-      heap_cur += nval;
-      cur = nxt;
-      ni = nchild;
-    }
-    if (ni) throw KhError{KH_EINVAL, "node store deeper than a 32-byte key allows"};
-    // the anchor map: only the new records enter it; rebuilt when it would pass half load
-    const uint64_t nnew = h->rn - rn0;
-    HIPCHK(hipEventRecord(c->ev[1], st));  // (stats: the rounds are done)
-    map_stage = true;
-    if (fill) {  // the resolved stubs leave the map and die; the new records take their anchors below
-      hipLaunchKernelGGL(k_map_delete, GRID(nfilled, BS), dim3(BS), 0, st, map_of(h), recs_of(h),
-                         (const uint32_t*)slist, nfilled, (const uint32_t*)nullptr, (uint64_t)0,
-                         (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p, (uint64_t*)nullptr);
-      LAUNCH_CHECK();
-      h->rdead += nfilled;
-    }
-    if (h->mcap == 0 || 2 * (h->mused + nnew + 1024) > h->mcap) {
-      map_rebuild(h, 1024);  // (syncs; with a savepoint open its map_epoch bump is the journal entry)
-    } else if (nnew) {
-      uint64_t* ilog = nullptr;
-      if (!h->sps.empty()) {  // journal: no saved records, the inserts' slot log
-        JSeg js = journal_reserve(h, 0, nnew);
-        js.dpos = js.ipos = h->jmap_n;
-        js.dn = 0;
-        js.in = nnew;
-        ilog = (uint64_t*)h->jmap.p + 3 * js.ipos;
-        h->jsegs.push_back(js);
-        h->jmap_n += nnew;
-      }
-      h->merr.ensure(64);
-      unsigned long long* err = (unsigned long long*)h->merr.p;
-      HIPCHK(hipMemsetAsync(err, 0, 16, st));
-      hipLaunchKernelGGL(k_map_insert, GRID(nnew, BS), dim3(BS), 0, st, map_of(h), recs_of(h), rn0, nnew,
-                         (const uint32_t*)nullptr, (uint64_t)0, err, err + 1, ilog);
-      LAUNCH_CHECK();
-      HIPCHK(hipMemcpyAsync(c->h_pinned, err, 16, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (c->h_pinned[0]) throw KhError{KH_EINTERNAL, "anchor map insert failed"};
-      h->mused += c->h_pinned[1];
-    }
-  } catch (...) {
-    if (map_stage) {
-      h->broken = true;  // the map may hold part of the load: only a rollback or a free from here
-    } else {
-      if (h->rn > rn0) {
-        (void)hipMemsetAsync((uint8_t*)h->recs.p + rn0 * REC_BYTES, 0, (h->rn - rn0) * REC_BYTES, st);
-        (void)hipStreamSynchronize(st);
-      }
-      h->rn = rn0;
-    }
-    throw;
-  }
-  h->heap_n = heap_cur;
-  h->nleaves += keys;
-  h->nstubs = h->nstubs + stubs_made - nfilled;
-  if (n_decoded) *n_decoded = decoded;
-  if (!fill) h->tid_bits = std::max(h->tid_bits, std::min(bits_for((uint64_t)max_id + 1) + 2, 32u));
-  ++h->epoch;
-  HIPCHK(hipEventRecord(c->ev[7], st));
-  HIPCHK(hipEventSynchronize(c->ev[7]));
-  if (stats) {
-    stats->n_inputs = k;
-    stats->n_leaves = h->nleaves;
-    stats->n_levels = rounds;
-    stats->n_node_hashes = n;
-    stats->t_total_ms = ev_ms(c->ev[6], c->ev[7]);
-    stats->t_sort_ms = ev_ms(c->ev[6], c->ev[0]);    // list checks, store hashing and sort
-    stats->t_branch_ms = ev_ms(c->ev[0], c->ev[1]);  // the rounds
-    stats->t_topo_ms = ev_ms(c->ev[1], c->ev[7]);    // the anchor map
-  }
-}
-
-// every trie the forest holds, ascending ids, with its root (read-only on the handle)
-static int forest_roots(kh_trie* h, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  const uint64_t n = h->rn;
-  *n_tries = 0;
-  if (n == 0) return KH_OK;
-  Layout L;
-  uint32_t *flag, *pos, *tot;
-  char* scr;
-  L.add_all(n, flag, pos);
-  L.add(scr, scan_scratch_bytes(n + 1, 4));
-  L.add(tot, 4);
-  place(h->gbuf, L);
-  const Recs R = recs_of(h);
-  hipLaunchKernelGGL(k_roots_flags, GRID(n, BS), dim3(BS), 0, st, R, n, flag);
-  LAUNCH_CHECK();
-  scan_exclusive<uint32_t>(flag, pos, n, tot, scr, st);
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t nt = (uint32_t)c->h_pinned[0];
-  *n_tries = nt;
-  if (nt > cap || (nt && (!h_tries || !h_roots32))) return set_err(KH_ENOSPC, "trie output too small");
-  if (nt == 0) return KH_OK;
-  Layout Lo;
-  uint32_t* dt;
-  uint64_t* dr;
-  Lo.add(dt, nt);
-  Lo.add(dr, nt * 4);
-  place(h->xbuf, Lo);
-  hipLaunchKernelGGL(k_roots_write, GRID(n, BS), dim3(BS), 0, st, R, n, (const uint32_t*)flag, (const uint32_t*)pos, nt,
-                     dt, dr);
-  LAUNCH_CHECK();
-  std::vector<uint32_t> t(nt), order(nt);
-  std::vector<uint8_t> r(nt * 32);
-  HIPCHK(hipMemcpyAsync(t.data(), dt, nt * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(r.data(), dr, nt * 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nt; ++i) order[i] = (uint32_t)i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t[a] < t[b]; });
-  for (uint64_t i = 0; i < nt; ++i) {
-    h_tries[i] = t[order[i]];
-    memcpy(h_roots32 + 32 * i, r.data() + 32ull * order[i], 32);
-  }
-  return KH_OK;
-}
-
-// drop whole tries: their live records listed (a scan: record order), out of the map, dead
-static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t* n_evicted) {
-  if (!h->sps.empty()) throw KhError{KH_EINVAL, "kh_forest_evict: a savepoint is open"};
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  *n_evicted = 0;
-  const uint64_t n = h->rn;
-  if (k == 0 || n == 0 || h->mcap == 0) return;
-  if (k >= (1ULL << 31)) throw KhError{KH_EINVAL, "trie list too large"};
-  std::vector<uint32_t> ids(tries, tries + k);
-  std::sort(ids.begin(), ids.end());
-  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-  const uint64_t nt = ids.size();
-  Layout L;
-  uint32_t *dt, *flag, *pos, *list;
-  unsigned long long* tot;
-  char* scr;
-  L.add(dt, nt);
-  L.add_all(n, flag, pos, list);
-  L.add(scr, scan_scratch_bytes(n + 1, 4));
-  L.add(tot, 8);
-  place(h->gbuf, L);
-  const Recs R = recs_of(h);
-  HIPCHK(hipMemcpyAsync(dt, ids.data(), nt * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
-  hipLaunchKernelGGL(k_evict_flags, GRID(n, BS), dim3(BS), 0, st, R, n, (const uint32_t*)dt, (uint32_t)nt, flag,
-                     tot + 1);
-  LAUNCH_CHECK();
-  scan_exclusive<uint32_t>(flag, pos, n, (uint32_t*)tot, scr, st);
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));  // (ids is a host temporary)
-  const uint64_t nl = (uint32_t)c->h_pinned[0], nkeys = c->h_pinned[1], ntries = c->h_pinned[2];
-  const uint64_t nstub = c->h_pinned[3];
-  if (nl == 0) return;
-  ++h->epoch;
-  hipLaunchKernelGGL(k_evict_list, GRID(n, BS), dim3(BS), 0, st, n, (const uint32_t*)flag, (const uint32_t*)pos, nl,
-                     list);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_map_delete, GRID(nl, BS), dim3(BS), 0, st, map_of(h), R, (const uint32_t*)list, nl,
-                     (const uint32_t*)nullptr, (uint64_t)0, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p,
-                     (uint64_t*)nullptr);
-  LAUNCH_CHECK();
-  HIPCHK(hipStreamSynchronize(st));
-  h->rdead += nl;
-  h->nleaves -= nkeys;
-  h->nstubs -= nstub;
-  *n_evicted = ntries;
-}
-
-// a host node store into the context's staging buffers (in_vals, in_voff), checked first:
-// KH_EINVAL before anything is staged
-static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint64_t n) {
-  if (n && !off) return set_err(KH_EINVAL, "null buffer");
-  if (n >= (1ULL << 31)) return set_err(KH_EINVAL, "node store too large");
-  for (uint64_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return set_err(KH_EINVAL, "node offsets must not decrease");
-  if (n && off[n] > off[0] && !enc) return set_err(KH_EINVAL, "null buffer");
-  std::vector<uint64_t> rel;
-  stage_packed(c, enc, off, n, rel);
-  HIPCHK(hipStreamSynchronize(c->st));
-  return KH_OK;
-}
-
-// A single trie opened from (root hash, node store on the device): the forest load of the one
-// trie id 0 into a fresh non-forest handle.  LOAD_FULL is kh_trie_open_nodes, LOAD_PARTIAL
-// kh_trie_open_partial.  The first missing node in frontier order (a partial open: only the root)
-// ends the open with KH_ENODE, its hash in missing32; a failed open leaves no handle.  own_ctx: the
-// handle moves to a private context (the *_host entry points; kh_trie_open_partial without one).
-static kh_trie* open_store(kh_ctx* c, const uint8_t* root32, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
-                           uint32_t flags, uint8_t* missing32, LoadMode mode, bool own_ctx) {
-  if (n && (!d_enc || !d_off)) throw KhError{KH_EINVAL, "null buffer"};
-  std::lock_guard<std::recursive_mutex> g(c->mu);
-  HIPCHK(hipSetDevice(c->dev));
-  kh_trie* h = trie_new(c, flags, false);
-  try {
-    const uint32_t id = 0;
-    uint32_t midx = 0;
-    uint8_t m32[32];
-    uint64_t nm = 0;
-    try {
-      forest_load(h, &id, root32, 1, d_enc, d_off, n, &midx, m32, 1, &nm, nullptr, mode);
-    } catch (...) {
-      if (nm && missing32) memcpy(missing32, m32, 32);
-      throw;
-    }
-    memcpy(h->root, root32, 32);
-    if (own_ctx) make_private(h);
-  } catch (...) {
-    delete h;
-    throw;
-  }
-  return h;
-}
-// the same from a host store, staged into the shared context
-static int open_store_host(const uint8_t* root32, const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t flags,
-                           uint8_t* missing32, kh_trie** out, LoadMode mode) {
-  if (!out || !root32 || (n && (!enc || !off))) return set_err(KH_EINVAL, "null input");
-  API_TRY({
-    kh_ctx* c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    const int rc = stage_store(c, enc, off, n);
-    if (rc != KH_OK) return rc;
-    *out = open_store(c, root32, (const uint8_t*)c->in_vals.p, (const uint64_t*)c->in_voff.p, n, flags, missing32, mode,
-                      true);
-  })
-}
-
-// The body of kh_forest_load_nodes, kh_forest_load_partial and kh_trie_fill_nodes (a fill: no trie
-// list, no missing list, and any handle) and of their _host forms, whose store is staged first
-// (stage_store makes its own checks of it).
-static int load_entry(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* enc,
-                      const uint64_t* off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
-                      uint64_t* n_missing, kh_stats* stats, LoadMode mode, uint64_t* n_decoded, bool host) {
-  if (n_missing) *n_missing = 0;
-  if (n_decoded) *n_decoded = 0;
-  if (mode == LOAD_FILL) {
-    if (!h) return set_err(KH_EINVAL, "null handle");
-  } else if (!h || !h->forest) {
-    return set_err(KH_EINVAL, "null handle or not a forest");
-  }
-  if ((k && (!tries || !roots32)) || (!host && n && (!enc || !off)) || (miss_cap && (!miss_idx || !miss32)))
-    return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    if (host) {
-      const int rc = stage_store(c, enc, off, n);
-      if (rc != KH_OK) return rc;
-      enc = (const uint8_t*)c->in_vals.p;
-      off = (const uint64_t*)c->in_voff.p;
-    }
-    forest_load(h, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, mode, n_decoded);
-  })
-}
-
-// ---- range scan (range.h; the kernels are csrc/range_kernels.hip's)
-__global__ void k_range_root(AMap M, Recs R, uint32_t t, uint32_t* items);
-__global__ void k_range_count(Recs R, KeyRange g, const uint32_t* items, uint64_t n, uint64_t* cnt,
-                              unsigned long long* expand);
-__global__ void k_range_fill(AMap M, Recs R, KeyRange g, const uint32_t* items, uint64_t n, const uint64_t* pos,
-                             uint64_t cut, uint32_t* out, unsigned long long* bad);
-__global__ void k_range_lens(Recs R, const uint32_t* items, uint64_t n1, uint64_t nent, uint64_t* len,
-                             unsigned long long* res);
-__global__ void k_range_fit(Recs R, const uint32_t* items, uint64_t n1, const uint64_t* pos, uint64_t nent,
-                            const uint64_t* total, uint64_t val_cap, unsigned long long* fit, uint64_t* next);
-__global__ void k_range_write(Recs R, const uint8_t* heap, const uint32_t* items, uint64_t k, const uint64_t* pos,
-                              uint64_t bytes, uint8_t* keys32, uint64_t* voff, uint8_t* vals);
-
-// what the rounds leave in the handle's gbuf for the write: the final frontier, the scanned value
-// offsets, the entries that fit
-struct RangePage {
-  const uint32_t* items = nullptr;
-  const uint64_t* pos = nullptr;
-  uint64_t k = 0, bytes = 0;
-  uint32_t rounds = 0;
-};
-static uint32_t g_range_rounds = 0;  // rounds of the last scan (khst_range_rounds: measurements only)
-extern "C" uint32_t khst_range_rounds() { return g_range_rounds; }
-
-// The rounds of a range scan (range.h) and the fit to val_cap.  Two frontiers of max_entries + 2
-// items, one sync of a pinned word triple a round.  KH_OK with the page described in P (P.k = 0:
-// an empty answer) and *n_entries, *val_bytes, *more, next32 set; KH_ENOSPC with *val_bytes;
-// KH_ENODE with missing32.
-static int range_scan(kh_trie* h, uint32_t trie, const uint8_t* origin32, const uint8_t* limit32, uint64_t max_entries,
-                      uint64_t val_cap, RangePage& P, uint64_t* n_entries, uint64_t* val_bytes, int* more,
-                      uint8_t* next32, uint8_t* missing32) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  KeyRange g;
-  memset(g.o, 0, 32);
-  memset(g.l, 0xFF, 32);
-  if (origin32) memcpy(g.o, origin32, 32);
-  if (limit32) memcpy(g.l, limit32, 32);
-  const uint32_t t = h->forest ? trie : 0u;
-  // (no more entries than records: the frontiers of a call asking for 2^31 - 1 stay the trie's size)
-  const uint64_t me = std::min<uint64_t>(max_entries, std::max<uint64_t>(h->rn, 1));
-  const uint64_t F = me + 2;
-  Layout L;
-  uint32_t *fa, *fb;
-  uint64_t* cnt;
-  unsigned long long* tot;
-  char* scr;
-  L.add(fa, F + 1);
-  L.add(fb, F + 1);
-  L.add(cnt, F + 1);
-  L.add(scr, scan_scratch_bytes(F + 1, 8));
-  L.add(tot, 16);
-  place(h->gbuf, L);
-  uint64_t ni = 0;
-  uint32_t rounds = 0;
-  uint32_t *cur = fa, *nxt = fb;
-  if (h->rn && h->mcap && key_cmp(g.o, g.l) <= 0) {
-    const Recs R = recs_of(h);
-    const AMap M = map_of(h);
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
-    // (an empty trie, or an id the forest does not hold: the item is NONE and the first count drops it)
-    hipLaunchKernelGGL(k_range_root, dim3(1), dim3(1), 0, st, M, R, t, fa);
-    LAUNCH_CHECK();
-    for (ni = 1; ni; ++rounds) {
-      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
-      hipLaunchKernelGGL(k_range_count, GRID(ni, BS), dim3(BS), 0, st, R, g, cur, ni, cnt, tot + 1);
-      LAUNCH_CHECK();
-      scan_exclusive<uint64_t>(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_range_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, g, cur, ni,
-                           (const uint64_t*)cnt, F, nxt, tot + 2);
-        LAUNCH_CHECK();
-      }
-      std::swap(cur, nxt);
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
-  }
-  P.rounds = g_range_rounds = rounds;
-  P.items = cur;
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *more = 0;
-    return KH_OK;
-  }
-  const Recs R = recs_of(h);
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_exclusive<uint64_t>(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  hipLaunchKernelGGL(k_range_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, n1, (const uint64_t*)cnt, nent,
-                     (const uint64_t*)(tot + 12), val_cap, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things in range
-    const uint64_t r = (uint32_t)c->h_pinned[3];
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    return set_err(KH_ENODE, "the range meets a subtree the handle does not hold (missing32 names its node)");
-  }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *more = k < n1;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the page's keys, offsets and values into device buffers (P.k > 0)
-static void range_emit(kh_trie* h, const RangePage& P, uint8_t* d_keys32, uint8_t* d_vals, uint64_t* d_voff) {
-  hipLaunchKernelGGL(k_range_write, GRID(P.k + 1, BS), dim3(BS), 0, h->c->st, recs_of(h), (const uint8_t*)h->heap.p,
-                     P.items, P.k, P.pos, P.bytes, d_keys32, d_voff, d_vals);
-  LAUNCH_CHECK();
-}
-static bool range_args_ok(kh_trie* h, uint64_t max_entries, const void* keys32, const void* voff,
-                          const uint64_t* n_entries, const uint64_t* val_bytes, const int* more, const uint8_t* next32) {
-  if (!h || !keys32 || !voff || !n_entries || !val_bytes || !more || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (max_entries == 0 || max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "max_entries must be in [1, 2^31)");
-    return false;
-  }
-  return true;
-}
-
-// ---- many ranges a call (range.h "MANY RANGES A CALL"; the kernels are csrc/range_kernels.hip's)
-__global__ void k_ranges_root(AMap M, Recs R, const uint32_t* tries, const uint8_t* origins32, const uint8_t* limits32,
-                              uint64_t nq, KeyRange* G, uint32_t* items, uint32_t* iq);
-__global__ void k_ranges_count(Recs R, const KeyRange* G, const uint32_t* items, const uint32_t* iq, uint64_t n,
-                               uint64_t* cnt, unsigned long long* expand);
-__global__ void k_ranges_fill(AMap M, Recs R, const KeyRange* G, const uint32_t* items, const uint32_t* iq, uint64_t n,
-                              const uint64_t* pos, uint64_t cut, uint32_t* out, uint32_t* outq, unsigned long long* bad);
-__global__ void k_ranges_fit(Recs R, const uint32_t* items, const uint32_t* iq, uint64_t n1, const uint64_t* pos,
-                             uint64_t nent, const uint64_t* total, uint64_t val_cap, uint64_t nq,
-                             unsigned long long* fit, uint64_t* next);
-__global__ void k_ranges_write(Recs R, const uint8_t* heap, const uint32_t* items, const uint32_t* iq, uint64_t k,
-                               const uint64_t* pos, uint64_t bytes, uint64_t nq, uint8_t* keys32, uint64_t* voff,
-                               uint8_t* vals, uint64_t* ent_off);
-
-// The rounds of nq range scans moving together and the fit to val_cap: the requests (device
-// arrays; d_tries NULL on a single trie, d_origins / d_limits nullable) through two segmented
-// frontiers of max_entries + 2 * nq items (range.h derives the cut), one sync of a pinned word
-// triple a round.  KH_OK with the answer described in P (P.k = 0: nothing in any range) and
-// *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with *val_bytes; KH_ENODE with missing32
-// and *n_done.
-static int ranges_scan(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins, const uint8_t* d_limits,
-                       uint64_t nq, uint64_t max_entries, uint64_t val_cap, RangePage& P, const uint32_t*& P_iq,
-                       uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done, uint8_t* next32,
-                       uint8_t* missing32) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
-  // (a request returns no more entries than the handle has records: the frontiers of a call asking
-  // for 2^31 - 1 follow the handle and nq)
-  const uint64_t me = std::min<uint64_t>(max_entries, nq * std::max<uint64_t>(h->rn, 1));
-  const uint64_t F = me + 2 * nq;
-  Layout L;
-  uint32_t *fa, *fb, *qa, *qb;
-  uint64_t* cnt;
-  unsigned long long* tot;
-  KeyRange* G;
-  char* scr;
-  L.add(fa, F + 1);
-  L.add(fb, F + 1);
-  L.add(qa, F + 1);
-  L.add(qb, F + 1);
-  L.add(cnt, F + 1);
-  L.add(G, nq);
-  L.add(scr, scan_scratch_bytes(F + 1, 8));
-  L.add(tot, 16);
-  place(h->gbuf, L);
-  uint64_t ni = 0;
-  uint32_t rounds = 0;
-  uint32_t *cur = fa, *nxt = fb, *curq = qa, *nxtq = qb;
-  if (h->rn && h->mcap) {
-    const Recs R = recs_of(h);
-    const AMap M = map_of(h);
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
-    hipLaunchKernelGGL(k_ranges_root, GRID(nq, BS), dim3(BS), 0, st, M, R, d_tries, d_origins, d_limits, nq, G, fa, qa);
-    LAUNCH_CHECK();
-    for (ni = nq; ni; ++rounds) {
-      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
-      hipLaunchKernelGGL(k_ranges_count, GRID(ni, BS), dim3(BS), 0, st, R, (const KeyRange*)G, cur, curq, ni, cnt,
-                         tot + 1);
-      LAUNCH_CHECK();
-      scan_exclusive<uint64_t>(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_ranges_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, (const KeyRange*)G, cur, curq,
-                           ni, (const uint64_t*)cnt, F, nxt, nxtq, tot + 2);
-        LAUNCH_CHECK();
-      }
-      std::swap(cur, nxt);
-      std::swap(curq, nxtq);
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
-  }
-  P.rounds = g_range_rounds = rounds;
-  P.items = cur;
-  P_iq = curq;
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *n_done = nq;
-    return KH_OK;
-  }
-  const Recs R = recs_of(h);
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_exclusive<uint64_t>(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  // fit: [4] k, [5] its bytes, [6] the length of entry k alone, [7] the request of thing k; [8..12) its key
-  hipLaunchKernelGGL(k_ranges_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, curq, n1, (const uint64_t*)cnt, nent,
-                     (const uint64_t*)(tot + 12), val_cap, nq, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things of the answer
-    const uint64_t r = (uint32_t)c->h_pinned[3], at = c->h_pinned[3] >> 32;
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 20, curq + at, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    *n_done = (uint32_t)c->h_pinned[20];
-    return set_err(KH_ENODE, "a range meets a subtree the handle does not hold (missing32 names its node, "
-                             "*n_done the request)");
-  }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *n_done = k < n1 ? c->h_pinned[7] : nq;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the answer's keys, value offsets, values and request offsets into device buffers (P.k > 0)
-static void ranges_emit(kh_trie* h, const RangePage& P, const uint32_t* iq, uint64_t nq, uint8_t* d_keys32,
-                        uint8_t* d_vals, uint64_t* d_voff, uint64_t* d_ent_off) {
-  hipLaunchKernelGGL(k_ranges_write, GRID(std::max(P.k, nq) + 1, BS), dim3(BS), 0, h->c->st, recs_of(h),
-                     (const uint8_t*)h->heap.p, P.items, iq, P.k, P.pos, P.bytes, nq, d_keys32, d_voff, d_vals,
-                     d_ent_off);
-  LAUNCH_CHECK();
-}
-static bool ranges_args_ok(kh_trie* h, const uint32_t* tries, uint64_t nq, uint64_t max_entries, const void* keys32,
-                           const void* voff, const void* ent_off, const uint64_t* n_entries, const uint64_t* val_bytes,
-                           const uint64_t* n_done, const uint8_t* next32) {
-  if (!h || !keys32 || !voff || !ent_off || !n_entries || !val_bytes || !n_done || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (nq == 0 || max_entries == 0 || nq >= (1ULL << 31) || max_entries >= (1ULL << 31) ||
-      nq + max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "nq and max_entries must be at least 1 and nq + max_entries < 2^31");
-    return false;
-  }
-  if (h->forest && !tries) {
-    set_err(KH_EINVAL, "a forest needs a trie id per request");
-    return false;
-  }
-  return true;
-}
-
-extern "C" {
-
-int kh_trie_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* origins32, const uint8_t* limits32,
-                        uint64_t nq, uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap,
-                        uint64_t* voff, uint64_t* ent_off, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
-                        uint8_t next32[32], uint8_t missing32[32]) {
-  if (!ranges_args_ok(h, tries, nq, max_entries, keys32, voff, ent_off, n_entries, val_bytes, n_done, next32))
-    return KH_EINVAL;
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    Layout Li;
-    uint32_t* dt;
-    uint8_t *dor, *dli;
-    Li.add(dt, nq, h->forest);
-    Li.add(dor, nq * 32, origins32 != nullptr);
-    Li.add(dli, nq * 32, limits32 != nullptr);
-    place(c->in_keys, Li);
-    if (dt) HIPCHK(hipMemcpyAsync(dt, tries, nq * 4, hipMemcpyHostToDevice, st));
-    if (dor) HIPCHK(hipMemcpyAsync(dor, origins32, nq * 32, hipMemcpyHostToDevice, st));
-    if (dli) HIPCHK(hipMemcpyAsync(dli, limits32, nq * 32, hipMemcpyHostToDevice, st));
-    RangePage P;
-    const uint32_t* iq = nullptr;
-    const int rc = ranges_scan(h, dt, dor, dli, nq, max_entries, val_cap, P, iq, n_entries, val_bytes, n_done, next32,
-                               missing32);
-    if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      voff[0] = 0;
-      memset(ent_off, 0, (nq + 1) * 8);
-      return KH_OK;
-    }
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dv;
-    uint64_t *dvo, *deo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(deo, nq + 1);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    ranges_emit(h, P, iq, nq, dk, dv, dvo, deo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ent_off, deo, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  })
-}
-
-int kh_dev_trie_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins32, const uint8_t* d_limits32,
-                       uint64_t nq, uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap,
-                       uint64_t* d_voff, uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes,
-                       uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!ranges_args_ok(h, d_tries, nq, max_entries, d_keys32, d_voff, d_ent_off, n_entries, val_bytes, n_done, next32))
-    return KH_EINVAL;
-  if ((((uintptr_t)d_voff) | ((uintptr_t)d_ent_off)) & 7) return set_err(KH_EINVAL, "voff and ent_off must be 8-byte aligned");
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    RangePage P;
-    const uint32_t* iq = nullptr;
-    const int rc = ranges_scan(h, h->forest ? d_tries : nullptr, d_origins32, d_limits32, nq, max_entries, val_cap, P,
-                               iq, n_entries, val_bytes, n_done, next32, missing32);
-    if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-      HIPCHK(hipMemsetAsync(d_ent_off, 0, (nq + 1) * 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      ranges_emit(h, P, iq, nq, d_keys32, d_vals, d_voff, d_ent_off);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
-  })
-}
-
-int kh_trie_range_host(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
-                       uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
-                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!range_args_ok(h, max_entries, keys32, voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    RangePage P;
-    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
-                              missing32);
-    if (rc != KH_OK) return rc;
-    voff[0] = 0;
-    if (P.k == 0) return KH_OK;
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dv;
-    uint64_t* dvo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    range_emit(h, P, dk, dv, dvo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  })
-}
-
-int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
-                      uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
-                      uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!range_args_ok(h, max_entries, d_keys32, d_voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    RangePage P;
-    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
-                              missing32);
-    if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      range_emit(h, P, d_keys32, d_vals, d_voff);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
-  })
-}
-
-int kh_trie_open_nodes(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
-                       uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  if (!c || !out || !root32) return set_err(KH_EINVAL, "null context, root or handle");
-  API_TRY({ *out = open_store(c, root32, d_enc, d_off, n, flags, missing32, LOAD_FULL, false); })
-}
-
-int kh_trie_open_nodes_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
-                            uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  return open_store_host(root32, enc, off, n, flags, missing32, out, LOAD_FULL);
-}
-
-int kh_forest_load_nodes(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
-                         const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
-                         uint64_t* n_missing, kh_stats* stats) {
-  return load_entry(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_FULL,
-                    nullptr, false);
-}
-
-int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
-                              const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32,
-                              uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
-  return load_entry(f, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_FULL,
-                    nullptr, true);
-}
-
-int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t cap, uint64_t* n_tries) {
-  if (!f || !f->forest || !n_tries) return set_err(KH_EINVAL, "null handle or output, or not a forest");
-  API_TRY({
-    HANDLE_LOCK(f);
-    HIPCHK(hipSetDevice(f->c->dev));
-    return forest_roots(f, h_tries, h_roots32, cap, n_tries);
-  })
-}
-
-int kh_forest_evict(kh_trie* f, const uint32_t* tries, uint64_t k, uint64_t* n_evicted) {
-  uint64_t dropped = 0;
-  if (n_evicted) *n_evicted = 0;
-  if (!f || !f->forest) return set_err(KH_EINVAL, "null handle or not a forest");
-  if (k && !tries) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(f);
-    HIPCHK(hipSetDevice(f->c->dev));
-    forest_evict(f, tries, k, &dropped);
-    if (n_evicted) *n_evicted = dropped;
-  })
-}
-
-int kh_trie_prove(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n, uint32_t flags,
-                  uint8_t* found, uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off,
-                  uint32_t* path_idx, uint64_t path_cap, uint64_t* path_off, uint64_t* n_nodes, uint64_t* rlp_len,
-                  uint64_t* n_path) {
-  if (!h || !path_off || !n_nodes || !rlp_len || !n_path) return set_err(KH_EINVAL, "null handle or outputs");
-  if (flags & ~(KH_PROVE_SHARED | KH_PROVE_TRIE_KEYS)) return set_err(KH_EINVAL, "unknown prove flag");
-  if (n && (!keys || !found)) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(h);
-    HIPCHK(hipSetDevice(h->c->dev));
-    return trie_prove(h, trie, keys, klen, n, flags, found, hashes32, node_cap, rlp, rlp_cap, off, path_idx, path_cap,
-                      path_off, n_nodes, rlp_len, n_path);
-  })
-}
-
-int kh_verify_proofs(const uint8_t* roots32, uint64_t nroots, const uint8_t* keys, uint32_t klen, uint64_t n,
-                     uint32_t flags, const uint8_t* rlp, const uint64_t* off, uint64_t n_nodes, const uint32_t* path_idx,
-                     const uint64_t* path_off, uint8_t* status, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
-                     uint64_t* val_bytes) {
-  if (!voff) return set_err(KH_EINVAL, "null value offsets");
-  if (flags & ~KH_HASH_KEYS) return set_err(KH_EINVAL, "unknown verify flag");
-  if (!(flags & KH_HASH_KEYS) && klen != 32) return set_err(KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS");
-  if (klen == 0 || klen > 4096) return set_err(KH_EINVAL, "bad key length");
-  if (n >= (1ULL << 31) || n_nodes >= (1ULL << 32)) return set_err(KH_EINVAL, "batch too large");
-  if (nroots != 1 && nroots != n) return set_err(KH_EINVAL, "one root, or one root per key");
-  if (n && (!roots32 || !keys || !status || !path_off || (n_nodes && !off))) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    return verify_proofs(roots32, nroots, keys, klen, n, flags, rlp, off, n_nodes, path_idx, path_off, status, vals,
-                         val_cap, voff, val_bytes);
-  })
-}
-
-
-int kh_trie_export_nodes(kh_trie* h, uint32_t trie_filter, uint32_t flags, kh_export_cursor* cur, uint8_t* hashes32,
-                         uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap, uint64_t* off, uint64_t* n_nodes,
-                         uint64_t* rlp_len, int* done) {
-  if (!h || !cur || !n_nodes || !rlp_len || !done) return set_err(KH_EINVAL, "null handle, cursor or size outputs");
-  if (flags & ~KH_EXPORT_VERIFY) return set_err(KH_EINVAL, "unknown export flag");
-  if ((node_cap && (!hashes32 || !off)) || (rlp_cap && !rlp)) return set_err(KH_EINVAL, "null output buffer");
-  if (!node_cap) rlp_cap = 0;  // (nothing can be written: sizes only)
-  API_TRY({
-    HANDLE_LOCK(h);
-    HIPCHK(hipSetDevice(h->c->dev));
-    *n_nodes = *rlp_len = 0;
-    *done = 0;
-    return trie_export(h, trie_filter, flags, cur, hashes32, node_cap, rlp, rlp_cap, off, n_nodes, rlp_len, done);
-  })
-}
-
-int kh_trie_nodes_by_hash(kh_trie* h, const uint8_t* hashes32, uint64_t n, uint8_t* found, uint8_t* rlp,
-                          uint64_t rlp_cap, uint64_t* off, uint64_t* rlp_len) {
-  if (!h || !off || !rlp_len) return set_err(KH_EINVAL, "null handle or outputs");
-  if (n > BYHASH_MAX) return set_err(KH_EINVAL, "at most 4096 hashes per call");
-  if (n && (!hashes32 || !found)) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(h);
-    HIPCHK(hipSetDevice(h->c->dev));
-    *rlp_len = 0;
-    if (n == 0) {
-      trie_settle(h);
-      off[0] = 0;
-      return KH_OK;
-    }
-    return trie_by_hash(h, hashes32, n, found, rlp, rlp_cap, off, rlp_len);
-  })
-}
-
-// ---- partial handles: open / load from a witness, fill, and what a refused commit needs
-int kh_trie_open_partial(kh_ctx* c, const uint8_t root32[32], const uint8_t* d_enc, const uint64_t* d_off, uint64_t n,
-                         uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  if (!out || !root32) return set_err(KH_EINVAL, "null root or handle");
-  API_TRY({
-    // (no context, as kh_forest_open: the one the *_host entry points use, and a private handle)
-    const bool host = !c;
-    if (host) c = shared_ctx(current_device());
-    *out = open_store(c, root32, d_enc, d_off, n, flags, missing32, LOAD_PARTIAL, host);
-  })
-}
-
-int kh_trie_open_partial_host(const uint8_t root32[32], const uint8_t* enc, const uint64_t* off, uint64_t n,
-                              uint32_t flags, uint8_t missing32[32], kh_trie** out) {
-  return open_store_host(root32, enc, off, n, flags, missing32, out, LOAD_PARTIAL);
-}
-
-int kh_forest_load_partial(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k, const uint8_t* d_enc,
-                           const uint64_t* d_off, uint64_t n, uint32_t* miss_idx, uint8_t* miss32, uint64_t miss_cap,
-                           uint64_t* n_missing, kh_stats* stats) {
-  return load_entry(f, tries, roots32, k, d_enc, d_off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL,
-                    nullptr, false);
-}
-
-int kh_forest_load_partial_host(kh_trie* f, const uint32_t* tries, const uint8_t* roots32, uint64_t k,
-                                const uint8_t* enc, const uint64_t* off, uint64_t n, uint32_t* miss_idx,
-                                uint8_t* miss32, uint64_t miss_cap, uint64_t* n_missing, kh_stats* stats) {
-  return load_entry(f, tries, roots32, k, enc, off, n, miss_idx, miss32, miss_cap, n_missing, stats, LOAD_PARTIAL,
-                    nullptr, true);
-}
-
-int kh_trie_fill_nodes(kh_trie* h, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n, uint64_t* n_decoded,
-                       kh_stats* stats) {
-  return load_entry(h, nullptr, nullptr, 0, d_enc, d_off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded,
-                    false);
-}
-
-int kh_trie_fill_nodes_host(kh_trie* h, const uint8_t* enc, const uint64_t* off, uint64_t n, uint64_t* n_decoded,
-                            kh_stats* stats) {
-  return load_entry(h, nullptr, nullptr, 0, enc, off, n, nullptr, nullptr, 0, nullptr, stats, LOAD_FILL, n_decoded,
-                    true);
-}
-
+// ---- a resident handle's small calls (the services' drivers and entry points stand in their
+// kernels' units: export_, prove_, load_, range_ and rangeverify_kernels.hip)
 int kh_trie_stubs(const kh_trie* h, uint64_t* n) {
   if (!h || !n) return set_err(KH_EINVAL, "null handle");
   HANDLE_LOCK(h);
@@ -7911,46 +6001,6 @@ int kh_trie_missing(const kh_trie* h, uint32_t* tries, uint8_t* hashes32, uint64
     memcpy(hashes32, h->miss_hashes.data(), k * 32);
   }
   return KH_OK;
-}
-
-int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
-                      uint8_t* need_flag, uint8_t* need32) {
-  if (!h) return set_err(KH_EINVAL, "null handle");
-  if (n && (!keys || !need_flag || !need32)) return set_err(KH_EINVAL, "null buffer");
-  API_TRY({
-    HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    query_check(h, trie, klen, n, h->flags & KH_HASH_KEYS);
-    if (n == 0) return KH_OK;
-    trie_settle(h);
-    if (!(h->nstubs && h->rn && h->mcap)) {  // no stub to reach
-      memset(need_flag, 0, n);
-      memset(need32, 0, n * 32);
-      return KH_OK;
-    }
-    Layout L;
-    uint8_t *dk, *df;
-    uint32_t* dt;
-    uint64_t *K, *dh;
-    L.add(K, n * 4 + 8);
-    L.add(dh, n * 4);
-    L.add(df, n + 64);
-    place(h->gbuf, L);
-    stage_query_keys(c, trie, keys, klen, n, dk, dt);
-    if (h->flags & KH_HASH_KEYS) {
-      hash_keys_to(st, (const uint8_t*)dk, klen, n, K);
-    } else {
-      HIPCHK(hipMemcpyAsync(K, dk, n * 32, hipMemcpyDeviceToDevice, st));
-    }
-    hipLaunchKernelGGL(k_need, GRID(n, BS), dim3(BS), 0, st, map_of(h), recs_of(h), (const uint64_t*)K,
-                       (const uint32_t*)dt, n, df, dh);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(need_flag, df, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(need32, dh, n * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  })
 }
 
 int kh_trie_compact(kh_trie* h, kh_trie_usage_t* before) {
@@ -7996,233 +6046,19 @@ int kh_trie_free(kh_trie* h) {
 // multi-GPU root over RCCL in one process (kh_trie_root_sharded)
 #include "sharded.h"
 
-// ---------------------------------------------------------------------------
-// range verification (rangeverify.h; the kernels are csrc/rangeverify_kernels.hip's)
-// ---------------------------------------------------------------------------
-#include "rangeverify.h"
-
-__global__ void k_rv_order(RvIn I, uint64_t ne, uint32_t* bad);
-__global__ void k_rv_walk_count(RvIn I, const uint32_t* bad, RvWalkOut W);
-__global__ void k_rv_plan(RvIn I, const uint32_t* bad, RvWalkOut W, uint8_t* status, uint8_t* more, uint64_t* miss32,
-                          uint64_t* cnt, uint32_t* inb);
-__global__ void k_rv_walk_fill(RvIn I, RvWalkOut W, const uint32_t* inb, const uint64_t* base, const uint32_t* segid,
-                               RvElems E);
-__global__ void k_rv_entries(RvIn I, uint64_t ne, const uint32_t* inb, const uint64_t* base, const uint32_t* segid,
-                             RvElems E);
-__global__ void k_rv_moved(RvElems E, const uint32_t* sidx, const int8_t* pd, uint64_t m, uint32_t* moved);
-__global__ void k_rv_final(RvIn I, const uint32_t* inb, const uint32_t* segid, const uint32_t* moved,
-                           const uint64_t* res_hash, const uint32_t* res_len, uint8_t* status);
-
-// nr ranges of ne entries in all against one node set, every input in HBM on c's stream; status,
-// more and missing32 (nullable) are host arrays.  The node set is hashed and sorted as the forest
-// load stages its store; the order check, the count pass of the boundary walk and the plan run
-// over every range; the ranges still undecided bring their entries and kept subtrees to ONE
-// segmented element build (run_build, the resident commit's), whose topology says which kept
-// subtree would have moved and whose segment roots are compared with the given ones.  Host syncs:
-// the store's sort (with nodes), the element total, run_build's own after its topology (with
-// elements), the results; kh_dev_verify_ranges adds one before, reading ent_off[0] and ent_off[nr].
-static void verify_ranges_dev(kh_ctx* c, const uint8_t* d_roots, const uint8_t* d_origins, const uint8_t* d_proved,
-                              uint64_t nr, const uint8_t* d_keys, const uint8_t* d_vals, const uint64_t* d_voff,
-                              const uint64_t* d_ent_off, uint64_t ne, const uint8_t* d_enc, const uint64_t* d_off,
-                              uint64_t n_nodes, uint8_t* status, uint8_t* more, uint8_t* missing32) {
-  hipStream_t st = c->st;
-  // ---- the node set, keyed by kec256 of each encoding
-  NStore NS{nullptr, nullptr, 0, d_enc, d_off};
-  if (n_nodes) {
-    Layout Ls;
-    uint64_t* hs;
-    SortIO S{};
-    Ls.add(hs, n_nodes * 4 + 4);
-    S.declare(Ls, n_nodes, n_nodes * 4 + 4, false, n_nodes + 1, n_nodes + 1, CTR_N);
-    place(c->rv_store, Ls);
-    S.K32 = hs;
-    S.n = n_nodes;
-    HIPCHK(hipMemsetAsync(S.ctr, 0, CTR_N * 8, st));
-    hipLaunchKernelGGL(k_kec_batch, GRID(n_nodes, BS), dim3(BS), 0, st, d_enc, d_off, n_nodes, hs);
-    LAUNCH_CHECK();
-    sort_dedup(c, S);
-    NS.hash = S.skey;
-    NS.idx = S.sidx;
-    NS.m = S.m;
-  }
-  const RvIn I{(const uint64_t*)d_roots, (const uint64_t*)d_origins, d_proved, nr, (const uint64_t*)d_keys, d_voff,
-               d_ent_off, NS};
-  // ---- order, the count pass of the walk, the plan
-  Layout Lw;
-  uint32_t *bad, *moved, *inb, *segid;
-  uint64_t *cnt, *base, *dmiss, *tot;
-  uint8_t *dst, *dmore;
-  char* scr;
-  RvWalkOut W{};
-  Lw.add_all(nr, bad, moved);  // (back to back: one memset)
-  Lw.add_all(2 * nr, W.st, W.cnt);
-  Lw.add(W.miss, 8 * nr);
-  Lw.add_all(nr + 1, cnt, base);
-  Lw.add_all(nr + 1, inb, segid);
-  Lw.add(dmiss, 4 * nr);
-  Lw.add_all(nr, dst, dmore);
-  Lw.add(scr, scan_scratch_bytes(nr + 1, 8));
-  Lw.add(tot, 8);
-  place(c->rv_ws, Lw);
-  HIPCHK(hipMemsetAsync(bad, 0, (size_t)((char*)(moved + nr) - (char*)bad), st));
-  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
-  if (ne) {
-    hipLaunchKernelGGL(k_rv_order, GRID(ne, BS), dim3(BS), 0, st, I, ne, bad);
-    LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(k_rv_walk_count, GRID(2 * nr, BS), dim3(BS), 0, st, I, (const uint32_t*)bad, W);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_rv_plan, GRID(nr, BS), dim3(BS), 0, st, I, (const uint32_t*)bad, W, dst, dmore, dmiss, cnt, inb);
-  LAUNCH_CHECK();
-  scan_exclusive<uint64_t>(cnt, base, nr, tot, scr, st);
-  scan_exclusive<uint32_t>(inb, segid, nr, (uint32_t*)(tot + 1), scr, st);
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t nel = c->h_pinned[0], nseg = (uint32_t)c->h_pinned[1];
-  if (nel >= (1ULL << 31)) throw KhError{KH_EINVAL, "kh_verify_ranges: entries and kept subtrees must be < 2^31"};
-  // ---- the rebuild: entries and kept subtrees of the undecided ranges, one segmented element build
-  if (nel) {
-    RvElems E{};
-    Layout Le;
-    Le.add(E.key, nel * 4);
-    Le.add(E.seg, nel);
-    Le.add(E.db, nel);
-    Le.add(E.ref, nel * 4);
-    Le.add_all(nel, E.rl, E.oldd);
-    Le.add(E.vo, nel);
-    Le.add(E.vl, nel);
-    Le.add(E.side, nel);
-    place(c->rv_el, Le);
-    E.cap = nel;
-    if (ne) {
-      hipLaunchKernelGGL(k_rv_entries, GRID(ne, BS), dim3(BS), 0, st, I, ne, (const uint32_t*)inb, (const uint64_t*)base,
-                         (const uint32_t*)segid, E);
-      LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_rv_walk_fill, GRID(2 * nr, BS), dim3(BS), 0, st, I, W, (const uint32_t*)inb,
-                       (const uint64_t*)base, (const uint32_t*)segid, E);
-    LAUNCH_CHECK();
-    ElemArgs EA{E.db, E.ref, E.rl, E.oldd, E.ref, E.rl, nullptr, &c->rv_elout, &c->rv_eloutb};
-    BuildArgs A{(const uint8_t*)E.key, 32, d_vals, (const uint64_t*)E.vo, nel,
-                nseg > 1 ? (const uint32_t*)E.seg : nullptr, nseg, 0, 0, false};
-    A.vlen = E.vl;
-    A.el = &EA;
-    A.dev_results = true;
-    BuildOut O;
-    run_build(c, A, O, nullptr);
-    const uint64_t m = c->T.m;
-    if (m != nel) throw KhError{KH_EINTERNAL, "kh_verify_ranges: duplicate elements"};
-    hipLaunchKernelGGL(k_rv_moved, GRID(m, BS), dim3(BS), 0, st, E, (const uint32_t*)c->T.sidx,
-                       (const int8_t*)c->T.lf_pd, m, moved);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_rv_final, GRID(nr, BS), dim3(BS), 0, st, I, (const uint32_t*)inb, (const uint32_t*)segid,
-                       (const uint32_t*)moved, (const uint64_t*)c->T.res_hash, (const uint32_t*)c->T.res_len, dst);
-    LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, c->T.ctr + CTR_ERR, 8, hipMemcpyDeviceToHost, st));
-  } else {
-    c->h_pinned[0] = 0;
-  }
-  // (the outputs are staged: an internal error writes nothing)
-  std::vector<uint8_t> hst(nr), hmore(nr), hmiss(missing32 ? nr * 32 : 0);
-  HIPCHK(hipMemcpyAsync(hst.data(), dst, nr, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(hmore.data(), dmore, nr, hipMemcpyDeviceToHost, st));
-  if (missing32) HIPCHK(hipMemcpyAsync(hmiss.data(), dmiss, nr * 32, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[0]) throw KhError{KH_EINTERNAL, "kh_verify_ranges: the element build flagged an invariant"};
-  memcpy(status, hst.data(), nr);
-  memcpy(more, hmore.data(), nr);
-  if (missing32) memcpy(missing32, hmiss.data(), nr * 32);
+// prims.h's scans and radix sort for the service units (host.h).  A kernel template is emitted into
+// the unit that instantiates it, where its first host-side use stands: these stand last, below every
+// use of this unit's own, so the instances stay this unit's alone and stay where they were
+// (DESIGN.md "Source layout").
+size_t khst::scan_scratch_size(uint64_t n, size_t elem) { return scan_scratch_bytes(n, elem); }
+size_t khst::radix_scratch_size(uint64_t n) { return radix_scratch_bytes(n); }
+void khst::scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* total, void* scratch, hipStream_t st) {
+  scan_exclusive<uint32_t>(in, out, n, total, scratch, st);
 }
-
-extern "C" {
-
-int kh_dev_verify_ranges(kh_ctx* c, const uint8_t* d_roots32, const uint8_t* d_origins32, const uint8_t* d_proved,
-                         uint64_t nr, const uint8_t* d_keys32, const uint8_t* d_vals, const uint64_t* d_voff,
-                         const uint64_t* d_ent_off, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n_nodes,
-                         uint8_t* status, uint8_t* more, uint8_t* missing32) {
-  if (nr >= (1ULL << 31) || n_nodes >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_verify_ranges: batch too large");
-  if (!d_ent_off || !d_voff || (nr && (!d_roots32 || !d_proved || !status || !more)) || (n_nodes && (!d_enc || !d_off)))
-    return set_err(KH_EINVAL, "kh_verify_ranges: null array");
-  // (roots, origins and keys are read as 64-bit words, the offsets are 64-bit words)
-  if ((((uintptr_t)d_roots32 | (uintptr_t)d_origins32 | (uintptr_t)d_keys32 | (uintptr_t)d_voff | (uintptr_t)d_ent_off |
-        (uintptr_t)d_off) & 7) != 0)
-    return set_err(KH_EINVAL, "kh_dev_verify_ranges: roots, origins, keys and offsets must be 8-byte aligned");
-  API_TRY({
-    if (!c) c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    if (nr == 0) return KH_OK;
-    // the entry total: ent_off[nr] - ent_off[0] (the arrays are used from ent_off[0] on)
-    uint64_t eo[2];
-    HIPCHK(hipMemcpyAsync(&eo[0], d_ent_off, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipMemcpyAsync(&eo[1], d_ent_off + nr, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (eo[0] != 0) return set_err(KH_EINVAL, "kh_dev_verify_ranges: ent_off[0] must be 0");
-    const uint64_t ne = eo[1];
-    if (ne >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_verify_ranges: batch too large");
-    if (ne && !d_keys32) return set_err(KH_EINVAL, "kh_verify_ranges: null array");
-    verify_ranges_dev(c, d_roots32, d_origins32, d_proved, nr, d_keys32, d_vals, d_voff, d_ent_off, ne, d_enc, d_off,
-                      n_nodes, status, more, missing32);
-  })
+void khst::scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* total, void* scratch, hipStream_t st) {
+  scan_exclusive<uint64_t>(in, out, n, total, scratch, st);
 }
-
-int kh_verify_ranges(const uint8_t* roots32, const uint8_t* origins32, const uint8_t* proved, uint64_t nr,
-                     const uint8_t* keys32, const uint8_t* vals, const uint64_t* voff, const uint64_t* ent_off,
-                     const uint8_t* enc, const uint64_t* off, uint64_t n_nodes, uint8_t* status, uint8_t* more,
-                     uint8_t* missing32) {
-  if (nr >= (1ULL << 31) || n_nodes >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_verify_ranges: batch too large");
-  if (!ent_off || !voff || (nr && (!roots32 || !proved || !status || !more)) || (n_nodes && (!enc || !off)))
-    return set_err(KH_EINVAL, "kh_verify_ranges: null array");
-  API_TRY({
-    for (uint64_t s = 0; s < nr; ++s)
-      if (ent_off[s + 1] < ent_off[s]) throw KhError{KH_EINVAL, "kh_verify_ranges: ent_off must not decrease"};
-    const uint64_t e0 = ent_off[0], ne = ent_off[nr] - e0;
-    if (ne >= (1ULL << 31)) throw KhError{KH_EINVAL, "kh_verify_ranges: batch too large"};
-    if (ne && !keys32) throw KhError{KH_EINVAL, "kh_verify_ranges: null array"};
-    for (uint64_t i = e0; i < e0 + ne; ++i) {
-      if (voff[i + 1] < voff[i]) throw KhError{KH_EINVAL, "kh_verify_ranges: voff must not decrease"};
-      if (voff[i + 1] - voff[i] > 0xFFFFFFFFull) throw KhError{KH_EINVAL, "kh_verify_ranges: a value longer than 2^32 - 1 bytes"};
-    }
-    for (uint64_t j = 0; j < n_nodes; ++j)
-      if (off[j + 1] < off[j]) throw KhError{KH_EINVAL, "kh_verify_ranges: off must not decrease"};
-    const uint64_t v0 = voff[e0], vb = voff[e0 + ne] - v0;
-    const uint64_t b0 = n_nodes ? off[0] : 0, nb = n_nodes ? off[n_nodes] - b0 : 0;
-    if (vb && !vals) throw KhError{KH_EINVAL, "kh_verify_ranges: null array"};
-    if (nr == 0) return KH_OK;
-    kh_ctx* c = shared_ctx(current_device());
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    // offsets rebased to zero; everything staged into one buffer
-    std::vector<uint64_t> reo(nr + 1), rvo(ne + 1), rno(n_nodes + 1, 0);
-    for (uint64_t s = 0; s <= nr; ++s) reo[s] = ent_off[s] - e0;
-    for (uint64_t i = 0; i <= ne; ++i) rvo[i] = voff[e0 + i] - v0;
-    for (uint64_t j = 0; j <= n_nodes && n_nodes; ++j) rno[j] = off[j] - b0;
-    Layout Li;
-    uint8_t *droots, *dorig, *dproved, *dkeys, *dvals, *denc;
-    uint64_t *dvoff, *deo, *dno;
-    Li.add(droots, nr * 32);
-    Li.add(dorig, nr * 32, origins32 != nullptr);
-    Li.add(dproved, nr);
-    Li.add(dkeys, ne * 32 + 32);
-    Li.add(dvals, vb + 64);
-    Li.add(denc, nb + 64);
-    Li.add(dvoff, ne + 1);
-    Li.add(deo, nr + 1);
-    Li.add(dno, n_nodes + 1);
-    place(c->rv_in, Li);
-    HIPCHK(hipMemcpyAsync(droots, roots32, nr * 32, hipMemcpyHostToDevice, st));
-    if (origins32) HIPCHK(hipMemcpyAsync(dorig, origins32, nr * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dproved, proved, nr, hipMemcpyHostToDevice, st));
-    if (ne) HIPCHK(hipMemcpyAsync(dkeys, keys32 + 32 * e0, ne * 32, hipMemcpyHostToDevice, st));
-    if (vb) HIPCHK(hipMemcpyAsync(dvals, vals + v0, vb, hipMemcpyHostToDevice, st));
-    if (nb) HIPCHK(hipMemcpyAsync(denc, enc + b0, nb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dvoff, rvo.data(), (ne + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(deo, reo.data(), (nr + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dno, rno.data(), (n_nodes + 1) * 8, hipMemcpyHostToDevice, st));
-    verify_ranges_dev(c, droots, dorig, dproved, nr, dkeys, dvals, dvoff, deo, ne, denc, dno, n_nodes, status, more,
-                      missing32);
-  })
+bool khst::sort_pairs_u64(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, uint64_t n, int lo_bit, int hi_bit,
+                          void* scratch, hipStream_t st) {
+  return radix_sort_pairs<uint64_t>(k0, v0, k1, v1, n, lo_bit, hi_bit, scratch, st);
 }
-
-}  // extern "C"

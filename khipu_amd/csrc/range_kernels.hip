@@ -1,17 +1,18 @@
-// Kernels of kh_trie_range_host / kh_dev_trie_range and of the batched kh_trie_ranges_host /
-// kh_dev_trie_ranges (k_ranges_*: range.h holds the bodies of both), a cold compilation
-// unit of their own like prove_kernels.hip and load_kernels.hip: the hot kernels of khst.hip keep
-// their placement (tests/test_code_layout.py).  Kernels only; khst.hip declares and launches them.
+// kh_trie_range_host / kh_dev_trie_range and the batched kh_trie_ranges_host / kh_dev_trie_ranges:
+// their kernels (k_ranges_*: range.h holds the bodies of both), then the host drivers range_scan and
+// ranges_scan and the C entry points (host.h).  A cold compilation unit of its own like
+// prove_kernels.hip and load_kernels.hip: the hot kernels of khst.hip keep their placement
+// (tests/test_code_layout.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "range.h"
+#include "host.h"
 
 using namespace khst;
 
 namespace {
-constexpr int BS = 256;
 constexpr uint32_t GROUPS = BS / EXP_LANES;  // frontier items per block of the fill
 }  // namespace
 
@@ -165,3 +166,417 @@ __global__ void __launch_bounds__(BS) k_ranges_write(Recs R, const uint8_t* heap
   }
   rng_write(R, heap, items[i], i, pos[i], keys32, voff, vals);
 }
+
+// ---------------------------------------------------------------------------
+// host: range scan (range.h)
+// ---------------------------------------------------------------------------
+// what the rounds leave in the handle's gbuf for the write: the final frontier, the scanned value
+// offsets, the entries that fit
+struct RangePage {
+  const uint32_t* items = nullptr;
+  const uint64_t* pos = nullptr;
+  uint64_t k = 0, bytes = 0;
+  uint32_t rounds = 0;
+};
+static uint32_t g_range_rounds = 0;  // rounds of the last scan (khst_range_rounds: measurements only)
+extern "C" uint32_t khst_range_rounds() { return g_range_rounds; }
+
+// The rounds of a range scan (range.h) and the fit to val_cap.  Two frontiers of max_entries + 2
+// items, one sync of a pinned word triple a round.  KH_OK with the page described in P (P.k = 0:
+// an empty answer) and *n_entries, *val_bytes, *more, next32 set; KH_ENOSPC with *val_bytes;
+// KH_ENODE with missing32.
+static int range_scan(kh_trie* h, uint32_t trie, const uint8_t* origin32, const uint8_t* limit32, uint64_t max_entries,
+                      uint64_t val_cap, RangePage& P, uint64_t* n_entries, uint64_t* val_bytes, int* more,
+                      uint8_t* next32, uint8_t* missing32) {
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  KeyRange g;
+  memset(g.o, 0, 32);
+  memset(g.l, 0xFF, 32);
+  if (origin32) memcpy(g.o, origin32, 32);
+  if (limit32) memcpy(g.l, limit32, 32);
+  const uint32_t t = h->forest ? trie : 0u;
+  // (no more entries than records: the frontiers of a call asking for 2^31 - 1 stay the trie's size)
+  const uint64_t me = std::min<uint64_t>(max_entries, std::max<uint64_t>(h->rn, 1));
+  const uint64_t F = me + 2;
+  Layout L;
+  uint32_t *fa, *fb;
+  uint64_t* cnt;
+  unsigned long long* tot;
+  char* scr;
+  L.add(fa, F + 1);
+  L.add(fb, F + 1);
+  L.add(cnt, F + 1);
+  L.add(scr, scan_scratch_size(F + 1, 8));
+  L.add(tot, 16);
+  place(h->gbuf, L);
+  uint64_t ni = 0;
+  uint32_t rounds = 0;
+  uint32_t *cur = fa, *nxt = fb;
+  if (h->rn && h->mcap && key_cmp(g.o, g.l) <= 0) {
+    const Recs R = recs_of(h);
+    const AMap M = map_of(h);
+    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
+    // (an empty trie, or an id the forest does not hold: the item is NONE and the first count drops it)
+    hipLaunchKernelGGL(k_range_root, dim3(1), dim3(1), 0, st, M, R, t, fa);
+    LAUNCH_CHECK();
+    for (ni = 1; ni; ++rounds) {
+      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
+      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
+      hipLaunchKernelGGL(k_range_count, GRID(ni, BS), dim3(BS), 0, st, R, g, cur, ni, cnt, tot + 1);
+      LAUNCH_CHECK();
+      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
+      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
+      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+      const uint64_t nn = std::min(total, F);  // the cut
+      if (nn) {
+        hipLaunchKernelGGL(k_range_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, g, cur, ni,
+                           (const uint64_t*)cnt, F, nxt, tot + 2);
+        LAUNCH_CHECK();
+      }
+      std::swap(cur, nxt);
+      ni = nn;
+      if (!expand) {
+        ++rounds;
+        break;
+      }
+    }
+  }
+  P.rounds = g_range_rounds = rounds;
+  P.items = cur;
+  P.pos = cnt;
+  P.k = P.bytes = 0;
+  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
+  if (n1 == 0) {
+    *n_entries = *val_bytes = 0;
+    *more = 0;
+    return KH_OK;
+  }
+  const Recs R = recs_of(h);
+  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
+  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
+  LAUNCH_CHECK();
+  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
+  hipLaunchKernelGGL(k_range_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, n1, (const uint64_t*)cnt, nent,
+                     (const uint64_t*)(tot + 12), val_cap, tot + 4, (uint64_t*)(tot + 8));
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things in range
+    const uint64_t r = (uint32_t)c->h_pinned[3];
+    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
+                          st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
+    return set_err(KH_ENODE, "the range meets a subtree the handle does not hold (missing32 names its node)");
+  }
+  const uint64_t k = c->h_pinned[4];
+  if (k == 0) {
+    *val_bytes = c->h_pinned[6];
+    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
+  }
+  P.k = k;
+  P.bytes = c->h_pinned[5];
+  *n_entries = k;
+  *val_bytes = P.bytes;
+  *more = k < n1;
+  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
+  return KH_OK;
+}
+// the page's keys, offsets and values into device buffers (P.k > 0)
+static void range_emit(kh_trie* h, const RangePage& P, uint8_t* d_keys32, uint8_t* d_vals, uint64_t* d_voff) {
+  hipLaunchKernelGGL(k_range_write, GRID(P.k + 1, BS), dim3(BS), 0, h->c->st, recs_of(h), (const uint8_t*)h->heap.p,
+                     P.items, P.k, P.pos, P.bytes, d_keys32, d_voff, d_vals);
+  LAUNCH_CHECK();
+}
+static bool range_args_ok(kh_trie* h, uint64_t max_entries, const void* keys32, const void* voff,
+                          const uint64_t* n_entries, const uint64_t* val_bytes, const int* more, const uint8_t* next32) {
+  if (!h || !keys32 || !voff || !n_entries || !val_bytes || !more || !next32) {
+    set_err(KH_EINVAL, "null handle or outputs");
+    return false;
+  }
+  if (max_entries == 0 || max_entries >= (1ULL << 31)) {
+    set_err(KH_EINVAL, "max_entries must be in [1, 2^31)");
+    return false;
+  }
+  return true;
+}
+
+// ---- many ranges a call (range.h "MANY RANGES A CALL")
+// The rounds of nq range scans moving together and the fit to val_cap: the requests (device
+// arrays; d_tries NULL on a single trie, d_origins / d_limits nullable) through two segmented
+// frontiers of max_entries + 2 * nq items (range.h derives the cut), one sync of a pinned word
+// triple a round.  KH_OK with the answer described in P (P.k = 0: nothing in any range) and
+// *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with *val_bytes; KH_ENODE with missing32
+// and *n_done.
+static int ranges_scan(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins, const uint8_t* d_limits,
+                       uint64_t nq, uint64_t max_entries, uint64_t val_cap, RangePage& P, const uint32_t*& P_iq,
+                       uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done, uint8_t* next32,
+                       uint8_t* missing32) {
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  // (a request returns no more entries than the handle has records: the frontiers of a call asking
+  // for 2^31 - 1 follow the handle and nq)
+  const uint64_t me = std::min<uint64_t>(max_entries, nq * std::max<uint64_t>(h->rn, 1));
+  const uint64_t F = me + 2 * nq;
+  Layout L;
+  uint32_t *fa, *fb, *qa, *qb;
+  uint64_t* cnt;
+  unsigned long long* tot;
+  KeyRange* G;
+  char* scr;
+  L.add(fa, F + 1);
+  L.add(fb, F + 1);
+  L.add(qa, F + 1);
+  L.add(qb, F + 1);
+  L.add(cnt, F + 1);
+  L.add(G, nq);
+  L.add(scr, scan_scratch_size(F + 1, 8));
+  L.add(tot, 16);
+  place(h->gbuf, L);
+  uint64_t ni = 0;
+  uint32_t rounds = 0;
+  uint32_t *cur = fa, *nxt = fb, *curq = qa, *nxtq = qb;
+  if (h->rn && h->mcap) {
+    const Recs R = recs_of(h);
+    const AMap M = map_of(h);
+    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
+    hipLaunchKernelGGL(k_ranges_root, GRID(nq, BS), dim3(BS), 0, st, M, R, d_tries, d_origins, d_limits, nq, G, fa, qa);
+    LAUNCH_CHECK();
+    for (ni = nq; ni; ++rounds) {
+      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
+      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
+      hipLaunchKernelGGL(k_ranges_count, GRID(ni, BS), dim3(BS), 0, st, R, (const KeyRange*)G, cur, curq, ni, cnt,
+                         tot + 1);
+      LAUNCH_CHECK();
+      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
+      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
+      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+      const uint64_t nn = std::min(total, F);  // the cut
+      if (nn) {
+        hipLaunchKernelGGL(k_ranges_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, (const KeyRange*)G, cur, curq,
+                           ni, (const uint64_t*)cnt, F, nxt, nxtq, tot + 2);
+        LAUNCH_CHECK();
+      }
+      std::swap(cur, nxt);
+      std::swap(curq, nxtq);
+      ni = nn;
+      if (!expand) {
+        ++rounds;
+        break;
+      }
+    }
+  }
+  P.rounds = g_range_rounds = rounds;
+  P.items = cur;
+  P_iq = curq;
+  P.pos = cnt;
+  P.k = P.bytes = 0;
+  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
+  if (n1 == 0) {
+    *n_entries = *val_bytes = 0;
+    *n_done = nq;
+    return KH_OK;
+  }
+  const Recs R = recs_of(h);
+  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
+  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
+  LAUNCH_CHECK();
+  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
+  // fit: [4] k, [5] its bytes, [6] the length of entry k alone, [7] the request of thing k; [8..12) its key
+  hipLaunchKernelGGL(k_ranges_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, curq, n1, (const uint64_t*)cnt, nent,
+                     (const uint64_t*)(tot + 12), val_cap, nq, tot + 4, (uint64_t*)(tot + 8));
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
+  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things of the answer
+    const uint64_t r = (uint32_t)c->h_pinned[3], at = c->h_pinned[3] >> 32;
+    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
+                          st));
+    HIPCHK(hipMemcpyAsync(c->h_pinned + 20, curq + at, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
+    *n_done = (uint32_t)c->h_pinned[20];
+    return set_err(KH_ENODE, "a range meets a subtree the handle does not hold (missing32 names its node, "
+                             "*n_done the request)");
+  }
+  const uint64_t k = c->h_pinned[4];
+  if (k == 0) {
+    *val_bytes = c->h_pinned[6];
+    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
+  }
+  P.k = k;
+  P.bytes = c->h_pinned[5];
+  *n_entries = k;
+  *val_bytes = P.bytes;
+  *n_done = k < n1 ? c->h_pinned[7] : nq;
+  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
+  return KH_OK;
+}
+// the answer's keys, value offsets, values and request offsets into device buffers (P.k > 0)
+static void ranges_emit(kh_trie* h, const RangePage& P, const uint32_t* iq, uint64_t nq, uint8_t* d_keys32,
+                        uint8_t* d_vals, uint64_t* d_voff, uint64_t* d_ent_off) {
+  hipLaunchKernelGGL(k_ranges_write, GRID(std::max(P.k, nq) + 1, BS), dim3(BS), 0, h->c->st, recs_of(h),
+                     (const uint8_t*)h->heap.p, P.items, iq, P.k, P.pos, P.bytes, nq, d_keys32, d_voff, d_vals,
+                     d_ent_off);
+  LAUNCH_CHECK();
+}
+static bool ranges_args_ok(kh_trie* h, const uint32_t* tries, uint64_t nq, uint64_t max_entries, const void* keys32,
+                           const void* voff, const void* ent_off, const uint64_t* n_entries, const uint64_t* val_bytes,
+                           const uint64_t* n_done, const uint8_t* next32) {
+  if (!h || !keys32 || !voff || !ent_off || !n_entries || !val_bytes || !n_done || !next32) {
+    set_err(KH_EINVAL, "null handle or outputs");
+    return false;
+  }
+  if (nq == 0 || max_entries == 0 || nq >= (1ULL << 31) || max_entries >= (1ULL << 31) ||
+      nq + max_entries >= (1ULL << 31)) {
+    set_err(KH_EINVAL, "nq and max_entries must be at least 1 and nq + max_entries < 2^31");
+    return false;
+  }
+  if (h->forest && !tries) {
+    set_err(KH_EINVAL, "a forest needs a trie id per request");
+    return false;
+  }
+  return true;
+}
+
+extern "C" {
+
+int kh_trie_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* origins32, const uint8_t* limits32,
+                        uint64_t nq, uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap,
+                        uint64_t* voff, uint64_t* ent_off, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
+                        uint8_t next32[32], uint8_t missing32[32]) {
+  if (!ranges_args_ok(h, tries, nq, max_entries, keys32, voff, ent_off, n_entries, val_bytes, n_done, next32))
+    return KH_EINVAL;
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    Layout Li;
+    uint32_t* dt;
+    uint8_t *dor, *dli;
+    Li.add(dt, nq, h->forest);
+    Li.add(dor, nq * 32, origins32 != nullptr);
+    Li.add(dli, nq * 32, limits32 != nullptr);
+    place(c->in_keys, Li);
+    if (dt) HIPCHK(hipMemcpyAsync(dt, tries, nq * 4, hipMemcpyHostToDevice, st));
+    if (dor) HIPCHK(hipMemcpyAsync(dor, origins32, nq * 32, hipMemcpyHostToDevice, st));
+    if (dli) HIPCHK(hipMemcpyAsync(dli, limits32, nq * 32, hipMemcpyHostToDevice, st));
+    RangePage P;
+    const uint32_t* iq = nullptr;
+    const int rc = ranges_scan(h, dt, dor, dli, nq, max_entries, val_cap, P, iq, n_entries, val_bytes, n_done, next32,
+                               missing32);
+    if (rc != KH_OK) return rc;
+    if (P.k == 0) {
+      voff[0] = 0;
+      memset(ent_off, 0, (nq + 1) * 8);
+      return KH_OK;
+    }
+    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
+    Layout Lo;
+    uint8_t *dk, *dv;
+    uint64_t *dvo, *deo;
+    Lo.add(dk, P.k * 32 + 64);
+    Lo.add(dvo, P.k + 1);
+    Lo.add(deo, nq + 1);
+    Lo.add(dv, P.bytes + 64);
+    place(c->out_emit, Lo);
+    ranges_emit(h, P, iq, nq, dk, dv, dvo, deo);
+    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ent_off, deo, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  })
+}
+
+int kh_dev_trie_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins32, const uint8_t* d_limits32,
+                       uint64_t nq, uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap,
+                       uint64_t* d_voff, uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes,
+                       uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]) {
+  if (!ranges_args_ok(h, d_tries, nq, max_entries, d_keys32, d_voff, d_ent_off, n_entries, val_bytes, n_done, next32))
+    return KH_EINVAL;
+  if ((((uintptr_t)d_voff) | ((uintptr_t)d_ent_off)) & 7) return set_err(KH_EINVAL, "voff and ent_off must be 8-byte aligned");
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    RangePage P;
+    const uint32_t* iq = nullptr;
+    const int rc = ranges_scan(h, h->forest ? d_tries : nullptr, d_origins32, d_limits32, nq, max_entries, val_cap, P,
+                               iq, n_entries, val_bytes, n_done, next32, missing32);
+    if (rc != KH_OK) return rc;
+    if (P.k == 0) {
+      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
+      HIPCHK(hipMemsetAsync(d_ent_off, 0, (nq + 1) * 8, c->st));
+    } else {
+      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
+      ranges_emit(h, P, iq, nq, d_keys32, d_vals, d_voff, d_ent_off);
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+  })
+}
+
+int kh_trie_range_host(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                       uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
+                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
+  if (!range_args_ok(h, max_entries, keys32, voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    RangePage P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
+                              missing32);
+    if (rc != KH_OK) return rc;
+    voff[0] = 0;
+    if (P.k == 0) return KH_OK;
+    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
+    Layout Lo;
+    uint8_t *dk, *dv;
+    uint64_t* dvo;
+    Lo.add(dk, P.k * 32 + 64);
+    Lo.add(dvo, P.k + 1);
+    Lo.add(dv, P.bytes + 64);
+    place(c->out_emit, Lo);
+    range_emit(h, P, dk, dv, dvo);
+    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  })
+}
+
+int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
+                      uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
+                      uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
+  if (!range_args_ok(h, max_entries, d_keys32, d_voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    RangePage P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
+                              missing32);
+    if (rc != KH_OK) return rc;
+    if (P.k == 0) {
+      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
+    } else {
+      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
+      range_emit(h, P, d_keys32, d_vals, d_voff);
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+  })
+}
+
+}  // extern "C"

@@ -51,7 +51,7 @@ struct RvIn {
   const uint64_t* ent_off;  // [nr+1]
   NStore S;                 // the node set, hashed and sorted
 };
-// the elements of the rebuild (khst.hip ElemArgs / forest.h Elems, input order)
+// the elements of the rebuild (host.h ElemArgs / forest.h Elems, input order)
 struct RvElems {
   uint64_t* key;   // [cap*4]
   uint32_t* seg;   // [cap] compact segment id of the element's range

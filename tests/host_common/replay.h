@@ -279,7 +279,7 @@ struct Result {
   std::vector<std::pair<uint32_t, std::array<uint8_t, 32>>> miss;
 };
 
-// the library's modes (khst.hip forest_load).  LOAD_FULL: a hash absent from the store is a
+// the library's modes (load_kernels.hip forest_load).  LOAD_FULL: a hash absent from the store is a
 // missing node; LOAD_PARTIAL: below the listed roots it is counted and written as a stub;
 // LOAD_FILL: round 0 is stubs, not roots, and an absent hash is a stub in every round.
 enum LoadMode { LOAD_FULL = 0, LOAD_PARTIAL = 1, LOAD_FILL = 2 };

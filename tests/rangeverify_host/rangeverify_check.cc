@@ -5,8 +5,8 @@
 // FILE, one record a line:
 //   N enchex                                   a node of the call's one node set
 //   R roothex originhex proved m key_1 val_1 .. key_m val_m    a range (val "-": empty)
-// All ranges are one call.  The program replays what khst.hip's verify_ranges_dev launches up to
-// the element build: the order check an entry, the count pass of the walk a (range, side), the
+// All ranges are one call.  The program replays what verify_ranges_dev (rangeverify_kernels.hip)
+// launches up to the element build: the order check an entry, the count pass of the walk a (range, side), the
 // plan a range, the exclusive scans, then the entries and the fill pass of the walk into element
 // arrays of exactly the scanned total -- a write anywhere else is AddressSanitizer's -- and checks
 // that every element was written exactly where the plan put it.  Per range:

@@ -21,7 +21,7 @@ import numpy as np
 
 SEED = 11
 
-# ---- khst.hip: `constexpr uint32_t CK_KEY_BITS = 12`, `bits_for`, `TIE_RUN_MAX = 64`, the tie
+# ---- khst.hip: `constexpr uint32_t CK_KEY_BITS = 12`, `bits_for` (host.h), `TIE_RUN_MAX = 64`, the tie
 # kernel's block of TF_ITEMS * BS = 1,024 sorted positions, and `n <= (1ull << 20) ? 8u : 0u`
 CK_KEY_BITS = 12
 TIE_RUN_MAX = 64
