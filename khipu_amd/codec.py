@@ -56,3 +56,43 @@ def account_rlp(nonce: int, balance: int, state_root: bytes = EMPTY_TRIE_HASH,
 def storage_value_rlp(v: int) -> bytes:
     """Storage slot value bytes, as rlpDataWordSerializer.toBytes (trie/package.scala:28-32)."""
     return rlp_str(uint_bytes(v))
+
+
+# ---- partial paths (snap's GetTrieNodes): a path is a sequence of nibbles, 0..64 of them
+def nibbles_to_path32(nibbles) -> bytes:
+    """A path as key bytes: packed big-endian, two nibbles a byte, zero-padded to 32 bytes (the
+    form a stub record keeps its key prefix in)."""
+    nib = list(nibbles) + [0] * (64 - len(nibbles))
+    return bytes((nib[2 * i] << 4) | nib[2 * i + 1] for i in range(32))
+
+
+def path32_to_nibbles(path32: bytes, n: int) -> list:
+    """The first n nibbles of a packed 32-byte path."""
+    return [(path32[i >> 1] >> 4) if i % 2 == 0 else (path32[i >> 1] & 0xF) for i in range(n)]
+
+
+def path_to_compact(nibbles) -> bytes:
+    """snap's wire form of a partial path: HexPrefix without the terminator flag (geth's
+    hexToCompact of a path that does not end a key) -- 0x00 then the nibbles in pairs when their
+    number is even, 0x1n then the rest when it is odd (1..33 bytes)."""
+    nib = list(nibbles)
+    if len(nib) > 64 or any(not 0 <= x < 16 for x in nib):
+        raise ValueError("a path is at most 64 nibbles, each 0..15")
+    if len(nib) % 2:
+        head, rest = bytes([0x10 | nib[0]]), nib[1:]
+    else:
+        head, rest = b"\x00", nib
+    return head + bytes((rest[i] << 4) | rest[i + 1] for i in range(0, len(rest), 2))
+
+
+def path_from_compact(b: bytes) -> list:
+    """The nibbles of a path in snap's wire form (path_to_compact's inverse)."""
+    if not b or len(b) > 33:
+        raise ValueError("a compact path is 1..33 bytes")
+    flag = b[0] >> 4
+    if flag > 1 or (flag == 0 and b[0] & 0xF):
+        raise ValueError("not a partial path: bad HexPrefix flag")
+    out = [b[0] & 0xF] if flag else []
+    for x in b[1:]:
+        out += [x >> 4, x & 0xF]
+    return out
