@@ -41,6 +41,9 @@
  *   kh_trie_prove           the nodes MerklePatriciaTrie.get visits (MerklePatriciaTrie.scala:90-147)
  *                           for a batch of keys: an eth_getProof answer, or a block's witness
  *   kh_verify_proofs        that walk re-done from a root over the listed nodes alone
+ *   kh_trie_diff_host       the keys two resident tries differ in (a parent state kept as a
+ *                           kh_trie_copy against the trie the blocks were committed on): the
+ *                           (upserts, deletes) of the kh_trie_apply that brings one to the other
  *   kh_verify_ranges        range responses (a page of kh_trie_range_host with its two boundary proofs,
  *                           or whole small tries) checked against their roots without a handle: nothing
  *                           left out between origin and the last key (no reference counterpart: khipu
@@ -712,6 +715,56 @@ int kh_dev_trie_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_ori
                        uint64_t nq, uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap,
                        uint64_t* d_voff, uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes,
                        uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]);
+
+/* ---- trie diff: the keys whose entries differ between two resident tries, in key order ----
+ * Side a is trie `trie_a` of handle a, side b trie `trie_b` of handle b: resident tries or forests
+ * on the same device (the ids are read on a forest and ignored on a single trie; a == b with two
+ * ids is allowed, the same (handle, id) on both sides is an empty answer; an id a forest does not
+ * hold, or an empty trie, is an empty side: every key of the other side is then a difference).
+ * Keys are TRIE keys (on KH_HASH_KEYS handles the kec256 values).  A difference is a key of
+ * [origin32, limit32] (both inclusive and nullable, as in kh_trie_range_host) whose entry differs
+ * between the sides: present on one side only, present on both with different value bytes, or
+ * present on both where exactly one entry is khipu's value-only branch -- the nodes differ then,
+ * and so do the roots; applying the upsert to a leaf is how khipu makes that branch.
+ *   The answer is the first differences in ascending key order: at most max_entries, cut to the
+ * longest prefix whose side-b values fit val_cap.  keys32 holds 32 * max_entries bytes, kinds
+ * max_entries bytes, voff max_entries + 1 slots: difference i is the key keys32[32i..) of kind
+ * kinds[i] with vals[voff[i]..voff[i+1]) = b's value for kinds 2 and 3, an empty span for kind 1 --
+ * so the KH_DIFF_ONLY_A keys are the deletes and the others the upserts of the kh_trie_apply that
+ * brings a to b.  *more = 1 and next32 = the first differing key not returned when one exists
+ * (continue with origin = next32), else *more = 0.  Read-only on both handles; with a savepoint
+ * open a call reads the commits since, as the range scan does.
+ *   Two subtrees are skipped, unread, exactly when both sides have a node that starts at the same
+ * nibble path with the same reference (a 32-byte hash, or the bytes of an embedded node): work and
+ * memory follow max_entries and the changed paths, not the tries (khipu_amd/csrc/diff.h).
+ *   Partial handles: a stub is a node that starts at the depth it records with the hash of the
+ * missing node (its extension, when present, starts at the stub's anchor with the reference the
+ * parent holds).  A stub skipped by the rule above costs nothing, so two partial handles that differ
+ * only where both hold nodes diff completely; a stub that is not skipped is a missing thing at its
+ * lowest key.
+ *   KH_ENOSPC  not even the first difference's value fits: *val_bytes is its size, nothing else is
+ *              written
+ *   KH_EINVAL  max_entries == 0 or >= 2^31, a null handle or output, handles on different devices
+ *   KH_ENODE   a missing thing is among the first max_entries + 1 things in range: missing32
+ *              (nullable) is the hash of the missing node, the lowest in key order (side a's when
+ *              both sides miss one at the same place); nothing else is written
+ * _host form with host buffers; kh_dev_trie_diff with keys32 / kinds / vals / voff device buffers
+ * (voff 8-byte aligned), on a's context stream (the scalar outputs are host words, valid on return). */
+#define KH_DIFF_ONLY_A 1   /* the key is in a only: a delete on the way from a to b */
+#define KH_DIFF_ONLY_B 2   /* the key is in b only: an upsert of b's value */
+#define KH_DIFF_CHANGED 3  /* in both; values differ, or exactly one side is a value-only branch */
+int kh_trie_diff_host(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b,
+                      const uint8_t origin32[32], const uint8_t limit32[32],
+                      uint64_t max_entries, uint64_t val_cap,
+                      uint8_t* keys32, uint8_t* kinds, uint8_t* vals, uint64_t* voff,
+                      uint64_t* n_entries, uint64_t* val_bytes, int* more,
+                      uint8_t next32[32], uint8_t missing32[32]);
+int kh_dev_trie_diff(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b,
+                     const uint8_t origin32[32], const uint8_t limit32[32],
+                     uint64_t max_entries, uint64_t val_cap,
+                     uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff,
+                     uint64_t* n_entries, uint64_t* val_bytes, int* more,
+                     uint8_t next32[32], uint8_t missing32[32]);
 
 /* ---- range verification: range responses checked against a root, without a handle ----
  * The receiving half of kh_trie_range_host + kh_trie_prove(KH_PROVE_TRIE_KEYS) (snap's ranges,

@@ -1436,6 +1436,65 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_ranges(JNIEnv* env, jclass cls,
   return (jlong)ne;
 }
 
+/* What differs between two resident tries, in key order (kh_trie_diff_host): side a is trie trieA of
+ * handleA, side b trie trieB of handleB (the ids are read on forests only; the two handles may be
+ * one forest).  The first differences of [origin, limit] (byte[32] each, or null: the lowest / the
+ * highest key) go into the caller's arrays: keys (32 bytes a difference), kinds (1: in a only, a
+ * delete on the way from a to b; 2: in b only; 3: in both and changed), b's values packed into vals
+ * with voff (an empty span for kind 1); at most min(keys.length / 32, kinds.length, voff.length - 1)
+ * differences, with values fitting vals.  sizes[0] = differences, sizes[1] = value bytes, sizes[2]
+ * = 1 when a difference in range was not returned: next (byte[32]) is its key, the origin of the
+ * next call.  Returns the count, or -1 when vals cannot hold even the first value (sizes[1] is its
+ * size: grow and call again).  A partial handle whose changed paths meet a missing subtree throws
+ * MPTNodeMissingException with the hash to fetch. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_diff(JNIEnv* env, jclass cls, jlong handleA, jint trieA,
+                                                     jlong handleB, jint trieB, jbyteArray origin, jbyteArray limit,
+                                                     jbyteArray keys, jbyteArray kinds, jbyteArray vals,
+                                                     jlongArray voff, jbyteArray next, jlongArray sizes) {
+  (void)cls;
+  if ((origin && len_of(env, origin) != 32) || (limit && len_of(env, limit) != 32) || len_of(env, next) < 32) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "diff: origin / limit / next must hold 32 bytes");
+    return 0;
+  }
+  uint64_t max_entries = (uint64_t)len_of(env, keys) / 32;
+  const jsize nvo = len_of(env, voff);
+  if ((uint64_t)(nvo > 0 ? nvo - 1 : 0) < max_entries) max_entries = (uint64_t)(nvo > 0 ? nvo - 1 : 0);
+  if ((uint64_t)len_of(env, kinds) < max_entries) max_entries = (uint64_t)len_of(env, kinds);
+  if (max_entries == 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "diff: keys / kinds / voff hold no difference");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint8_t* og = in_b(env, &b, origin);
+  const uint8_t* lm = in_b(env, &b, limit);
+  uint8_t* ks = out_buf(env, &b, keys, 1);
+  uint8_t* kd = out_buf(env, &b, kinds, 1);
+  uint8_t* vs = out_buf(env, &b, vals, 1);
+  uint64_t* vo = out_buf(env, &b, voff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t ne = 0, nb = 0;
+  int more = 0;
+  uint8_t nx[32] = {0}, miss[32] = {0};
+  const int rc = kh_trie_diff_host(H(handleA), (uint32_t)trieA, H(handleB), (uint32_t)trieB, og, lm, max_entries,
+                                   (uint64_t)len_of(env, vals), ks, kd, vs, vo, &ne, &nb, &more, nx, miss);
+  if (rc == KH_OK) {
+    put_b(env, keys, ks, 32 * ne);
+    put_b(env, kinds, kd, ne);
+    put_b(env, vals, vs, nb);
+    put_l(env, voff, vo, ne + 1);
+    if (more) put_b(env, next, nx, 32);
+  }
+  bufs_free(&b);
+  const jlong sz[3] = {(jlong)ne, (jlong)nb, (jlong)more};
+  put_l(env, sizes, sz, 3);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh_hash(env, rc, miss);
+    return 0;
+  }
+  return (jlong)ne;
+}
+
 /* The proofs prove returned (or a peer sent) checked against roots (32 bytes: one root for every
  * key; or 32 per key): status[i] one of KH_PROOF_*, the values of the KH_PROOF_VALUE keys packed
  * into vals with voff[n + 1].  nNodes table nodes in rlp / off.  flags: KH_HASH_KEYS.  Returns the

@@ -25,6 +25,10 @@ KH_EXPORT_VERIFY = 0x1  # kh_trie_export_nodes: re-hash every encoding against i
 KH_FOUND_UNKNOWN = 2  # kh_trie_get / kh_trie_prove: the key's walk reaches a stub of a partial handle
 KH_PROVE_SHARED = 0x1  # kh_trie_prove: every (record, node) once in the table (a block witness)
 KH_PROVE_TRIE_KEYS = 0x2  # kh_trie_prove: the keys are trie keys already (a range scan's), not hashed
+# kh_trie_diff_host kinds
+KH_DIFF_ONLY_A = 1   # the key is in a only: a delete on the way from a to b
+KH_DIFF_ONLY_B = 2   # the key is in b only: an upsert of b's value
+KH_DIFF_CHANGED = 3  # in both; values differ, or exactly one side is a value-only branch
 # kh_verify_proofs statuses
 KH_PROOF_ABSENT = 0     # valid: the key is not in the trie
 KH_PROOF_VALUE = 1      # valid: the value is returned
@@ -57,7 +61,7 @@ EXPORTS = (
     "kh_forest_evict", "kh_trie_open_partial", "kh_trie_open_partial_host", "kh_forest_load_partial",
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
-    "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges",
+    "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
 )
 
 
@@ -209,6 +213,11 @@ def lib():
     L.kh_dev_trie_ranges.argtypes = L.kh_trie_ranges_host.argtypes
     L.kh_verify_ranges.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
     L.kh_dev_verify_ranges.argtypes = [vp] + L.kh_verify_ranges.argtypes
+    L.kh_trie_diff_host.argtypes = [vp, u32, vp, u32, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.POINTER(u64),
+                                    ctypes.POINTER(u64), ctypes.POINTER(i32), vp, vp]
+    L.kh_dev_trie_diff.argtypes = L.kh_trie_diff_host.argtypes
+    L.khst_diff_rounds.restype = u32   # (measurements: the last diff's rounds and selected items)
+    L.khst_diff_visited.restype = u64
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

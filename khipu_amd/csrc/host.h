@@ -490,6 +490,17 @@ void trie_settle(kh_trie* h);
 
 // every entry point on a resident handle serialises on its home context (khst.h: reentrant)
 #define HANDLE_LOCK(h) std::lock_guard<std::recursive_mutex> handle_lock_(*(h)->lk)
+// both handles of a block commit: one mutex when they share a context, else both (std::lock:
+// no deadlock against another call locking them in the other order)
+struct PairLock {
+  std::unique_lock<std::recursive_mutex> a, b;
+  PairLock(std::recursive_mutex* x, std::recursive_mutex* y) : a(*x, std::defer_lock), b(*y, std::defer_lock) {
+    if (x == y)
+      a.lock();
+    else
+      std::lock(a, b);
+  }
+};
 
 inline Recs recs_of(kh_trie* h) {
   return recs_at((uint8_t*)h->recs.p);

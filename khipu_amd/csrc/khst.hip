@@ -3573,18 +3573,6 @@ void khst::trie_settle(kh_trie* h) {
   if (h->pend_fresh) h->mused += h->pend[1];
 }
 
-// both handles of a block commit: one mutex when they share a context, else both (std::lock:
-// no deadlock against another call locking them in the other order)
-struct PairLock {
-  std::unique_lock<std::recursive_mutex> a, b;
-  PairLock(std::recursive_mutex* x, std::recursive_mutex* y) : a(*x, std::defer_lock), b(*y, std::defer_lock) {
-    if (x == y)
-      a.lock();
-    else
-      std::lock(a, b);
-  }
-};
-
 // grow a device array, keeping its first `keep` bytes
 void khst::regrow(DevBuf& b, size_t keep, size_t bytes, hipStream_t st) {
   if (bytes <= b.cap) return;

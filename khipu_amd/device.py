@@ -501,6 +501,22 @@ class ResidentTrie(_Versioned):
         self.ctx._sync()
         return _ranges_proof(self.h, requests, max_entries, val_cap, False)
 
+    def diff(self, other, origin=None, limit=None, max_entries=1024, val_cap=1 << 20, other_trie=None):
+        """One page of what differs between this trie (side a) and `other` (side b: a ResidentTrie, or
+        trie other_trie of a ResidentForest), in key order (kh_trie_diff_host; trie_diff): (entries,
+        more, next), entries = [(key, kind, value)]."""
+        self.ctx._sync()
+        other.ctx._sync()
+        return trie_diff(self.h, None, other.h, other_trie, origin, limit, max_entries, val_cap)
+
+    def changes(self, other, chunk=1024, other_trie=None):
+        """diff() paged to the end: (upserts, deletes) with trie keys -- committed on a copy of this
+        trie they give other's root (on a handle that hashes its keys they are the kec256 values, for
+        a replica that stores trie keys)."""
+        self.ctx._sync()
+        other.ctx._sync()
+        return _diff_changes(self.h, None, other.h, other_trie, chunk)
+
     @property
     def root_hash(self):
         return self.root
@@ -599,6 +615,71 @@ def _range_items(h, origin, limit, chunk, trie, val_cap=1 << 20):
         if not more:
             return
         origin = nxt
+
+
+def trie_diff(ha, trie_a, hb, trie_b, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+    """One page of the differences between two resident tries (kh_trie_diff_host): (entries, more,
+    next), entries = [(key, kind, value)] in key order -- kind KH_DIFF_ONLY_A (value b""),
+    KH_DIFF_ONLY_B or KH_DIFF_CHANGED with side b's value; next is the first differing key not
+    returned when more.  Keys are trie keys.  KH_ENOSPC raises KhError with .val_bytes, KH_ENODE
+    (partial handles) MPTNodeMissingException with the hash to fetch in .missing."""
+    n = int(max_entries)
+    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
+    ob = np.frombuffer(origin, np.uint8).copy() if origin is not None else None
+    lb = np.frombuffer(limit, np.uint8).copy() if limit is not None else None
+    if (ob is not None and ob.size != 32) or (lb is not None and lb.size != 32):
+        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
+    keys = np.zeros(32 * room, np.uint8)
+    kinds = np.zeros(room, np.uint8)
+    vals = np.zeros(max(int(val_cap), 1), np.uint8)
+    voff = np.zeros(room + 1, np.uint64)
+    ne, vb, more = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    nxt = np.zeros(32, np.uint8)
+    miss = np.zeros(32, np.uint8)
+    rc = lib().kh_trie_diff_host(ha, 0 if trie_a is None else trie_a, hb, 0 if trie_b is None else trie_b,
+                                 ob.ctypes.data if ob is not None else None,
+                                 lb.ctypes.data if lb is not None else None, n, int(val_cap), keys.ctypes.data,
+                                 kinds.ctypes.data, vals.ctypes.data, voff.ctypes.data, ctypes.byref(ne),
+                                 ctypes.byref(vb), ctypes.byref(more), nxt.ctypes.data, miss.ctypes.data)
+    if rc == _lib.KH_ENODE:
+        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+        e.missing = miss.tobytes()
+        raise e
+    if rc == _lib.KH_ENOSPC:
+        e = _lib.KhError(rc, lib().kh_last_error().decode())
+        e.val_bytes = int(vb.value)
+        raise e
+    check(rc)
+    k = int(ne.value)
+    return ([(keys[32 * i:32 * i + 32].tobytes(), int(kinds[i]), vals[int(voff[i]):int(voff[i + 1])].tobytes())
+             for i in range(k)], bool(more.value), nxt.tobytes() if more.value else None)
+
+
+def _diff_changes(ha, trie_a, hb, trie_b, chunk, val_cap=1 << 20):
+    """Every difference, paged by next (val_cap grows on KH_ENOSPC), as the (upserts, deletes) of the
+    commit that brings side a to side b."""
+    ups, dels, origin = [], [], None
+    while True:
+        try:
+            ents, more, nxt = trie_diff(ha, trie_a, hb, trie_b, origin, None, chunk, val_cap)
+        except _lib.KhError as e:
+            if e.code != _lib.KH_ENOSPC:
+                raise
+            val_cap = max(2 * val_cap, e.val_bytes)
+            continue
+        for k, kind, v in ents:
+            if kind == _lib.KH_DIFF_ONLY_A:
+                dels.append(k)
+            else:
+                ups.append((k, v))
+        if not more:
+            return ups, dels
+        origin = nxt
+
+
+def diff_counters():
+    """(rounds past the root pair, frontier items selected) of the last diff: measurements only."""
+    return int(lib().khst_diff_rounds()), int(lib().khst_diff_visited())
 
 
 def _range_proof(h, origin, limit, max_entries, val_cap, trie):
@@ -1046,6 +1127,20 @@ class ResidentForest(_Versioned):
         proved flags: (pages, n_done, next, table, proved), as verify_ranges takes them."""
         self.ctx._sync()
         return _ranges_proof(self.h, requests, max_entries, val_cap, True)
+
+    def diff(self, trie, other, other_trie=None, origin=None, limit=None, max_entries=1024, val_cap=1 << 20):
+        """One page of what differs between trie `trie` (side a) and `other` (side b: a ResidentTrie, or
+        trie other_trie of a ResidentForest, this one included), in key order (kh_trie_diff_host;
+        trie_diff): (entries, more, next), entries = [(key, kind, value)]."""
+        self.ctx._sync()
+        other.ctx._sync()
+        return trie_diff(self.h, trie, other.h, other_trie, origin, limit, max_entries, val_cap)
+
+    def changes(self, trie, other, other_trie=None, chunk=1024):
+        """diff() paged to the end: the (upserts, deletes) that bring trie `trie` to side b."""
+        self.ctx._sync()
+        other.ctx._sync()
+        return _diff_changes(self.h, trie, other.h, other_trie, chunk)
 
     def last_roots(self):
         """{trie_id: root} of the last commit (kh_forest_last_roots; also after block_commit)."""
