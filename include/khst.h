@@ -44,6 +44,8 @@
  *   kh_trie_diff_host       the keys two resident tries differ in (a parent state kept as a
  *                           kh_trie_copy against the trie the blocks were committed on): the
  *                           (upserts, deletes) of the kh_trie_apply that brings one to the other
+ *   kh_trie_diffs_host      the same for many trie pairs of two forests in one call: every storage
+ *                           trie a block touched, under one budget
  *   kh_verify_ranges        range responses (a page of kh_trie_range_host with its two boundary proofs,
  *                           or whole small tries) checked against their roots without a handle: nothing
  *                           left out between origin and the last key (no reference counterpart: khipu
@@ -765,6 +767,59 @@ int kh_dev_trie_diff(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b,
                      uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff,
                      uint64_t* n_entries, uint64_t* val_bytes, int* more,
                      uint8_t next32[32], uint8_t missing32[32]);
+
+/* ---- batched trie diff: many trie pairs of two forests (or many ranges of one pair) in one call ----
+ * nq requests answered in request order under ONE entry and byte budget (a replica's (upserts,
+ * deletes) of every storage trie a block touched, a parent version kept as a kh_trie_copy of the
+ * forest).  Request q is kh_trie_diff_host's contract applied to trie tries_a[q] of handle a against
+ * trie tries_b[q] of handle b over [origins32[32q..), limits32[32q..)], both inclusive.  tries_b
+ * NULL: tries_b = tries_a (two versions of one forest).  On a single-trie handle that side's ids are
+ * ignored and may be NULL.  origins32 NULL: every origin 32 zero bytes; limits32 NULL: every limit 32
+ * bytes of 0xFF.  Empty requests: the same (handle, id) on both sides, an id neither side holds, two
+ * empty tries, origin > limit, and a pair with equal roots (its two root probes and no round).  An id
+ * held by one side only makes every key of the other side a difference.  The same pair may be named
+ * by several requests.  Keys, kinds, side-b values and the value-only-branch rule are
+ * kh_trie_diff_host's.
+ *   The answer is the concatenation, in request order, of each request's differences in ascending
+ * key order, cut to its longest prefix of at most max_entries differences IN TOTAL whose side-b
+ * values fit val_cap IN TOTAL.  keys32 holds 32 * max_entries bytes, kinds max_entries bytes, voff
+ * max_entries + 1 slots, ent_off nq + 1 slots: difference i is the key keys32[32i..) of kind kinds[i]
+ * with the value vals[voff[i]..voff[i+1]); request q's differences are ent_off[q] .. ent_off[q+1],
+ * and ent_off[nq] = *n_entries.
+ *   *n_done is the number of leading requests answered completely; *n_done == nq: every difference
+ * asked for was returned.  Otherwise request *n_done is the cut one: its differences so far are
+ * returned (none when the cut falls exactly on its first difference), next32 is its first differing
+ * key not returned (continue with that as its origin), and the requests after it are unanswered --
+ * their spans are empty and they are to be asked again.  Empty requests before the cut one count as
+ * done.
+ *   Read-only on both handles; with a savepoint open a call reads the commits since.  All requests
+ * move through the rounds of the walk together: a call costs the rounds of its deepest request, and
+ * its work and memory follow max_entries + nq and the changed paths, not the tries
+ * (khipu_amd/csrc/diff.h).
+ *   KH_ENOSPC  not even the first difference of the whole answer fits: *val_bytes is its size,
+ *              nothing else is written
+ *   KH_EINVAL  nq == 0, max_entries == 0, nq + max_entries >= 2^31, a null handle or output, tries_a
+ *              NULL on a forest side (a forest a, or a forest b without tries_b), handles on
+ *              different devices
+ *   KH_ENODE   a missing thing is among the first max_entries + 1 things of the concatenated answer:
+ *              missing32 (nullable) is the hash of its node (side a's when both sides miss one at
+ *              the same place) and *n_done the index of the request it belongs to; nothing else is
+ *              written.  A stub that is skipped costs nothing, as in the single call.
+ * _host form with host buffers; kh_dev_trie_diffs with tries_a / tries_b / origins32 / limits32 /
+ * keys32 / kinds / vals / voff / ent_off device buffers (voff and ent_off 8-byte aligned), on a's
+ * context stream (the scalar outputs are host words, valid on return). */
+int kh_trie_diffs_host(kh_trie* a, const uint32_t* tries_a, kh_trie* b, const uint32_t* tries_b,
+                       const uint8_t* origins32, const uint8_t* limits32, uint64_t nq,
+                       uint64_t max_entries, uint64_t val_cap,
+                       uint8_t* keys32, uint8_t* kinds, uint8_t* vals, uint64_t* voff, uint64_t* ent_off,
+                       uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
+                       uint8_t next32[32], uint8_t missing32[32]);
+int kh_dev_trie_diffs(kh_trie* a, const uint32_t* d_tries_a, kh_trie* b, const uint32_t* d_tries_b,
+                      const uint8_t* d_origins32, const uint8_t* d_limits32, uint64_t nq,
+                      uint64_t max_entries, uint64_t val_cap,
+                      uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff, uint64_t* d_ent_off,
+                      uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
+                      uint8_t next32[32], uint8_t missing32[32]);
 
 /* ---- range verification: range responses checked against a root, without a handle ----
  * The receiving half of kh_trie_range_host + kh_trie_prove(KH_PROVE_TRIE_KEYS) (snap's ranges,

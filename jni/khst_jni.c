@@ -1495,6 +1495,75 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_diff(JNIEnv* env, jclass cls, j
   return (jlong)ne;
 }
 
+/* Many trie pairs in one call (kh_trie_diffs_host): nq requests -- trie triesA[q] of handleA against
+ * trie triesB[q] of handleB (the ids are read on forests only and may be null on a single trie;
+ * triesB null: triesA, two versions of one forest), range [origins[32q..), limits[32q..)] (either
+ * array null: the lowest / the highest key for every request) -- answered in request order under
+ * ONE budget: at most min(keys.length / 32, kinds.length, voff.length - 1) differences in total,
+ * with values fitting vals in total.  The differences go into keys / kinds / vals / voff as in diff;
+ * request q's differences are entOff[q] .. entOff[q+1] (entOff holds nq + 1).  sizes[0] =
+ * differences, sizes[1] = value bytes, sizes[2] = the number of leading requests answered
+ * completely: when it is less than nq, that request is the cut one, next (byte[32]) its first
+ * differing key not returned, and the requests after it are to be asked again.  Returns the count,
+ * or -1 when vals cannot hold even the first value (sizes[1] is its size).  A partial handle whose
+ * changed paths meet a missing subtree throws MPTNodeMissingException with the hash to fetch,
+ * sizes[2] the request it belongs to.  Region copies only, no critical region, as ranges. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_diffs(JNIEnv* env, jclass cls, jlong handleA, jintArray triesA,
+                                                      jlong handleB, jintArray triesB, jbyteArray origins,
+                                                      jbyteArray limits, jint nq, jbyteArray keys, jbyteArray kinds,
+                                                      jbyteArray vals, jlongArray voff, jlongArray entOff,
+                                                      jbyteArray next, jlongArray sizes) {
+  (void)cls;
+  if (nq <= 0 || (triesA && len_of(env, triesA) < nq) || (triesB && len_of(env, triesB) < nq) ||
+      (origins && (uint64_t)len_of(env, origins) < 32ull * (uint64_t)nq) ||
+      (limits && (uint64_t)len_of(env, limits) < 32ull * (uint64_t)nq) || len_of(env, entOff) < nq + 1 ||
+      len_of(env, next) < 32) {
+    throw_cls(env, "java/lang/IllegalArgumentException",
+              "diffs: nq must be positive; triesA / triesB / origins / limits / entOff must hold nq requests, next 32 bytes");
+    return 0;
+  }
+  uint64_t max_entries = (uint64_t)len_of(env, keys) / 32;
+  const jsize nvo = len_of(env, voff);
+  if ((uint64_t)(nvo > 0 ? nvo - 1 : 0) < max_entries) max_entries = (uint64_t)(nvo > 0 ? nvo - 1 : 0);
+  if ((uint64_t)len_of(env, kinds) < max_entries) max_entries = (uint64_t)len_of(env, kinds);
+  if (max_entries == 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "diffs: keys / kinds / voff hold no difference");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint32_t* ta = in_i(env, &b, triesA);
+  const uint32_t* tb = in_i(env, &b, triesB);
+  const uint8_t* og = in_b(env, &b, origins);
+  const uint8_t* lm = in_b(env, &b, limits);
+  uint8_t* ks = out_buf(env, &b, keys, 1);
+  uint8_t* kd = out_buf(env, &b, kinds, 1);
+  uint8_t* vs = out_buf(env, &b, vals, 1);
+  uint64_t* vo = out_buf(env, &b, voff, 8);
+  uint64_t* eo = out_buf(env, &b, entOff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t ne = 0, nb = 0, nd = 0;
+  uint8_t nx[32] = {0}, miss[32] = {0};
+  const int rc = kh_trie_diffs_host(H(handleA), ta, H(handleB), tb, og, lm, (uint64_t)nq, max_entries,
+                                    (uint64_t)len_of(env, vals), ks, kd, vs, vo, eo, &ne, &nb, &nd, nx, miss);
+  if (rc == KH_OK) {
+    put_b(env, keys, ks, 32 * ne);
+    put_b(env, kinds, kd, ne);
+    put_b(env, vals, vs, nb);
+    put_l(env, voff, vo, ne + 1);
+    put_l(env, entOff, eo, (uint64_t)nq + 1);
+    if (nd < (uint64_t)nq) put_b(env, next, nx, 32);
+  }
+  bufs_free(&b);
+  const jlong sz[3] = {(jlong)ne, (jlong)nb, (jlong)nd};
+  put_l(env, sizes, sz, 3);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh_hash(env, rc, miss);
+    return 0;
+  }
+  return (jlong)ne;
+}
+
 /* The proofs prove returned (or a peer sent) checked against roots (32 bytes: one root for every
  * key; or 32 per key): status[i] one of KH_PROOF_*, the values of the KH_PROOF_VALUE keys packed
  * into vals with voff[n + 1].  nNodes table nodes in rlp / off.  flags: KH_HASH_KEYS.  Returns the

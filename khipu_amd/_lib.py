@@ -62,6 +62,7 @@ EXPORTS = (
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
     "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
+    "kh_trie_diffs_host", "kh_dev_trie_diffs",
 )
 
 
@@ -218,6 +219,11 @@ def lib():
     L.kh_dev_trie_diff.argtypes = L.kh_trie_diff_host.argtypes
     L.khst_diff_rounds.restype = u32   # (measurements: the last diff's rounds and selected items)
     L.khst_diff_visited.restype = u64
+    L.kh_trie_diffs_host.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, vp, vp, vp, vp, vp, ctypes.POINTER(u64),
+                                     ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp]
+    L.kh_dev_trie_diffs.argtypes = L.kh_trie_diffs_host.argtypes
+    L.khst_diffs_rounds.restype = u32  # (measurements: the last batched diff's rounds and selected items)
+    L.khst_diffs_visited.restype = u64
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

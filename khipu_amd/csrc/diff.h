@@ -47,8 +47,31 @@
 //             round on a path and the closing round.  The items are then one-sided entries (kinds
 //             1 and 2), pairs of entries at one key (kind 3) and items with a stub (missing).
 //
+// MANY PAIRS A CALL (kh_trie_diffs_host, kh_dev_trie_diffs): nq requests (trie of a, trie of b,
+// origin, limit) answered in request order under one entry and byte budget -- range.h's segmented
+// frontier run over two tries.  An item is (ra, rb, D, q), ordered by (request, key).  Round 0 has
+// one thread a request: its KeyRange into an nq-long array, its root pair at place q, (NONE, NONE)
+// when the request is empty or its root pair is skipped (df_plan drops that item: no compaction).
+// A round is the round above with every item selected against ITS OWN request's range, and the fill
+// writes the item's request beside each item it places (both halves of a split): a request's items
+// stay between its neighbours', so the order holds by construction and no slot is claimed with an
+// atomic.  All requests move together: a call takes the rounds of its deepest request.
+//   the cut   the new frontier is the first max_entries + 2 * nq items.  Per request at most the
+//             item on origin's path and the item on limit's path can turn out empty, and limit's is
+//             the last of its segment; every other item holds a thing (the argument above, per
+//             segment).  Let X be the item that holds thing max_entries + 1 of the concatenated
+//             answer, in request x.  The empty items before X are at most two for each of the
+//             x <= nq - 1 requests before x and the origin item of x: 2 * nq - 1.  The items up to X
+//             that hold a thing are at most max_entries + 1.  So X is among the first
+//             max_entries + 2 * nq items, and one item fewer can lose it (tests/test_diffs_host.py
+//             builds that input).
+//   the end   a round in which no item of any request expanded or split.  Then the first
+//             max_entries + 1 things, the lowest stub, the fit to val_cap and the write are the
+//             single call's; ent_off[q] is rng_ent_off over the returned items' requests, and the
+//             cut request is that of thing k, the first not returned.
+//
 // KH_HD bodies only, shared by range_kernels.hip (16 lanes an item, lane c owning child c) and the
-// host replay of tests/diff_host.
+// host replays of tests/diff_host and tests/diffs_host.
 #pragma once
 #include "range.h"
 
@@ -155,14 +178,17 @@ KH_HD bool df_expands(uint32_t sel) { return (sel & (0xFFFFu | DF_SPLIT_A | DF_S
 
 // lane c of item (ra, rb, D) with selection sel (the plan with the skipped lanes cleared) and scanned
 // base: what the lane owns goes to its place in the next frontier when that lies before the cut;
-// false: the anchor map lacks a child a mask names (a corrupt map)
+// false: the anchor map lacks a child a mask names (a corrupt map).  oq (a segmented frontier): the
+// item's request q is written beside what is placed, both halves of a split included.
 KH_HD bool df_fill_lane(const DSide& A, uint32_t ra, const DSide& B, uint32_t rb, uint32_t D, uint32_t sel,
-                        uint32_t c, uint64_t base, uint64_t cut, uint32_t* oa, uint32_t* ob, uint32_t* od) {
+                        uint32_t c, uint64_t base, uint64_t cut, uint32_t* oa, uint32_t* ob, uint32_t* od,
+                        uint32_t* oq = nullptr, uint32_t q = 0) {
   if (sel & DF_SELF) {
     if (c == 0 && base < cut) {
       oa[base] = ra;
       ob[base] = rb;
       od[base] = D;
+      if (oq) oq[base] = q;
     }
     return true;
   }
@@ -177,6 +203,7 @@ KH_HD bool df_fill_lane(const DSide& A, uint32_t ra, const DSide& B, uint32_t rb
         oa[at] = a_now ? ra : NONE;
         ob[at] = a_now ? NONE : rb;
         od[at] = D;
+        if (oq) oq[at] = q;
       }
       ++at;
     }
@@ -190,7 +217,34 @@ KH_HD bool df_fill_lane(const DSide& A, uint32_t ra, const DSide& B, uint32_t rb
   oa[at] = ca;
   ob[at] = cb;
   od[at] = m + 1;
+  if (oq) oq[at] = q;
   return ca != NONE || cb != NONE;
+}
+
+// ---- many pairs a call: round 0 of request q.  Its KeyRange goes to G[q] and its root pair to place
+// q: (NONE, NONE), which df_plan drops, for an empty request (origin > limit, the same (handle, id)
+// on both sides, no root on either side) and for a root pair that is skipped (equal tries).  ta / tb:
+// the requests' trie ids (NULL: a single trie, id 0); has_a / has_b: the side has records at all;
+// same: both sides are one handle.  true: the request has something to walk.
+KH_HD bool df_request(const DSide& A, const uint32_t* ta, bool has_a, const DSide& B, const uint32_t* tb, bool has_b,
+                      bool same, const uint8_t* origins32, const uint8_t* limits32, uint64_t q, KeyRange* G,
+                      uint32_t* ia, uint32_t* ib, uint32_t* id, uint32_t* iq) {
+  KeyRange g;
+  const bool ok = rng_request(origins32, limits32, q, &g);
+  G[q] = g;
+  const uint32_t ida = ta ? ta[q] : 0u, idb = tb ? tb[q] : 0u;
+  uint32_t ra = NONE, rb = NONE;
+  if (ok && !(same && ida == idb)) {
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    if (has_a) ra = map_find(A.M, A.R, ida, 0, zero);
+    if (has_b) rb = map_find(B.M, B.R, idb, 0, zero);
+    if (df_skip(A, ra, B, rb, 0)) ra = rb = NONE;
+  }
+  ia[q] = ra;
+  ib[q] = rb;
+  id[q] = 0;
+  iq[q] = (uint32_t)q;
+  return ra != NONE || rb != NONE;
 }
 
 // ---- after the last round: an item is a difference or holds a stub

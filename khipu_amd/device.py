@@ -517,6 +517,16 @@ class ResidentTrie(_Versioned):
         other.ctx._sync()
         return _diff_changes(self.h, None, other.h, other_trie, chunk)
 
+    def diffs(self, requests, other, max_entries=1024, val_cap=1 << 20, other_trie=None):
+        """Many ranges of the one pair (this trie, `other`) in one call (kh_trie_diffs_host;
+        trie_diffs): requests = [(origin or None, limit or None)] -> (pages, n_done, next), pages[q] =
+        [(key, kind, value)].  other: a ResidentTrie, or trie other_trie of a ResidentForest."""
+        self.ctx._sync()
+        other.ctx._sync()
+        b_forest = isinstance(other, ResidentForest)
+        return trie_diffs(self.h, False, other.h, b_forest,
+                          [(other_trie if b_forest else None, None, o, l) for o, l in requests], max_entries, val_cap)
+
     @property
     def root_hash(self):
         return self.root
@@ -680,6 +690,96 @@ def _diff_changes(ha, trie_a, hb, trie_b, chunk, val_cap=1 << 20):
 def diff_counters():
     """(rounds past the root pair, frontier items selected) of the last diff: measurements only."""
     return int(lib().khst_diff_rounds()), int(lib().khst_diff_visited())
+
+
+def trie_diffs(ha, a_forest, hb, b_forest, requests, max_entries=1024, val_cap=1 << 20):
+    """Many trie pairs in one call (kh_trie_diffs_host).  requests: [(trie_a, trie_b, origin, limit)]
+    -- trie_a / trie_b the ids on a forest side (ignored on a single trie; trie_b None: trie_a),
+    origin / limit None: the lowest / the highest key.
+    -> (pages, n_done, next): pages[q] = [(key, kind, value)] of request q, the requests answered in
+    order under max_entries differences and val_cap side-b value bytes IN TOTAL; n_done leading
+    requests are answered completely; when n_done < len(requests), request n_done is the cut one,
+    next its first differing key not returned (else None), and the requests after it are unanswered
+    (empty pages).  Keys are trie keys.  KH_ENOSPC raises KhError with .val_bytes; KH_ENODE raises
+    MPTNodeMissingException with the hash to fetch in .missing and the request in .request."""
+    reqs = [tuple(q) for q in requests]
+    nq = len(reqs)
+    n = int(max_entries)
+    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
+    if any(x is not None and len(x) != 32 for _, _, o, l in reqs for x in (o, l)):
+        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
+    ta = tb = None
+    if a_forest or b_forest:
+        ta = np.asarray([t or 0 for t, _, _, _ in reqs] + [0], np.uint32)
+    if b_forest and any(u is not None for _, u, _, _ in reqs):
+        tb = np.asarray([(t or 0) if u is None else u for t, u, _, _ in reqs] + [0], np.uint32)
+    ob = lb = None
+    if any(o is not None for _, _, o, _ in reqs):
+        ob = np.frombuffer(b"".join(o if o is not None else b"\0" * 32 for _, _, o, _ in reqs), np.uint8).copy()
+    if any(l is not None for _, _, _, l in reqs):
+        lb = np.frombuffer(b"".join(l if l is not None else b"\xff" * 32 for _, _, _, l in reqs), np.uint8).copy()
+    keys = np.zeros(32 * room, np.uint8)
+    kinds = np.zeros(room, np.uint8)
+    vals = np.zeros(max(int(val_cap), 1), np.uint8)
+    voff = np.zeros(room + 1, np.uint64)
+    eoff = np.zeros(nq + 1, np.uint64)
+    ne, vb, nd = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    nxt = np.zeros(32, np.uint8)
+    miss = np.zeros(32, np.uint8)
+    ptr = lambda x: x.ctypes.data if x is not None else None  # noqa: E731
+    rc = lib().kh_trie_diffs_host(ha, ptr(ta), hb, ptr(tb), ptr(ob), ptr(lb), nq, n, int(val_cap), keys.ctypes.data,
+                                  kinds.ctypes.data, vals.ctypes.data, voff.ctypes.data, eoff.ctypes.data,
+                                  ctypes.byref(ne), ctypes.byref(vb), ctypes.byref(nd), nxt.ctypes.data,
+                                  miss.ctypes.data)
+    if rc == _lib.KH_ENODE:
+        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+        e.missing = miss.tobytes()
+        e.request = int(nd.value)
+        raise e
+    if rc == _lib.KH_ENOSPC:
+        e = _lib.KhError(rc, lib().kh_last_error().decode())
+        e.val_bytes = int(vb.value)
+        raise e
+    check(rc)
+    assert int(eoff[nq]) == int(ne.value)
+    kb, vbuf = keys[:32 * int(ne.value)].tobytes(), vals[:int(vb.value)].tobytes()
+    pages = [[(kb[32 * i:32 * i + 32], int(kinds[i]), vbuf[int(voff[i]):int(voff[i + 1])])
+              for i in range(int(eoff[q]), int(eoff[q + 1]))] for q in range(nq)]
+    done = int(nd.value)
+    return pages, done, nxt.tobytes() if done < nq else None
+
+
+def _diffs_changes(ha, a_forest, hb, b_forest, pairs, chunk, val_cap=1 << 20):
+    """Every difference of every pair [(trie_a, trie_b)], kh_trie_diffs_host paged to the end by
+    n_done / next (val_cap grows on KH_ENOSPC): [(upserts, deletes)] per pair."""
+    out = [([], []) for _ in pairs]
+    reqs = [(t, u, None, None) for t, u in pairs]
+    first = 0  # the pair reqs[0] belongs to
+    while reqs:
+        try:
+            pages, done, nxt = trie_diffs(ha, a_forest, hb, b_forest, reqs, chunk, val_cap)
+        except _lib.KhError as e:
+            if e.code != _lib.KH_ENOSPC:
+                raise
+            val_cap = max(2 * val_cap, e.val_bytes)
+            continue
+        for q, page in enumerate(pages[:done + 1]):
+            ups, dels = out[first + q]
+            for k, kind, v in page:
+                if kind == _lib.KH_DIFF_ONLY_A:
+                    dels.append(k)
+                else:
+                    ups.append((k, v))
+        if done == len(reqs):
+            break
+        reqs = [(reqs[done][0], reqs[done][1], nxt, None)] + reqs[done + 1:]
+        first += done
+    return out
+
+
+def diffs_counters():
+    """(rounds past the root pairs, frontier items selected) of the last batched diff: measurements only."""
+    return int(lib().khst_diffs_rounds()), int(lib().khst_diffs_visited())
 
 
 def _range_proof(h, origin, limit, max_entries, val_cap, trie):
@@ -1141,6 +1241,40 @@ class ResidentForest(_Versioned):
         self.ctx._sync()
         other.ctx._sync()
         return _diff_changes(self.h, trie, other.h, other_trie, chunk)
+
+    def diffs(self, requests, other=None, max_entries=1024, val_cap=1 << 20):
+        """Many trie pairs in one call (kh_trie_diffs_host; trie_diffs): requests = [(trie, other_trie
+        or None, origin or None, limit or None)], trie of this forest (side a) against other_trie
+        (None: the same id) of `other` (side b: a ResidentForest, None for this one, or a
+        ResidentTrie) -> (pages, n_done, next), pages[q] = [(key, kind, value)]."""
+        other = self if other is None else other
+        self.ctx._sync()
+        other.ctx._sync()
+        return trie_diffs(self.h, True, other.h, isinstance(other, ResidentForest), requests, max_entries, val_cap)
+
+    def changes_all(self, other, tries=None, chunk=4096):
+        """diffs() of trie t of this forest against trie t of `other`, for every t of `tries`, paged
+        to the end by n_done / next: {t: (upserts, deletes)} for the ids that differ -- committed on
+        this forest they give other's tries.  tries=None: the ids of roots() of both sides, those
+        whose roots are equal dropped on the host."""
+        if tries is None:
+            mine, theirs = self.roots(), other.roots()
+            tries = sorted(t for t in set(mine) | set(theirs) if mine.get(t) != theirs.get(t))
+        tries = list(tries)
+        self.ctx._sync()
+        other.ctx._sync()
+        got = _diffs_changes(self.h, True, other.h, True, [(t, None) for t in tries], chunk)
+        return {t: ud for t, ud in zip(tries, got) if ud[0] or ud[1]}
+
+    def copy(self):
+        """An independent resident forest holding the current version of every trie (kh_trie_copy):
+        how a parent version of a storage forest is kept."""
+        h = ctypes.c_void_p()
+        self.ctx._sync()
+        check(lib().kh_trie_copy(self.h, ctypes.byref(h)))
+        f = ResidentForest.__new__(ResidentForest)
+        f.ctx, f.dev, f.h, f.hash_keys = self.ctx, self.dev, h, self.hash_keys
+        return f
 
     def last_roots(self):
         """{trie_id: root} of the last commit (kh_forest_last_roots; also after block_commit)."""
