@@ -1,8 +1,11 @@
 // kh_trie_range_host / kh_dev_trie_range and the batched kh_trie_ranges_host / kh_dev_trie_ranges:
-// their kernels (k_ranges_*: range.h holds the bodies of both), then the host drivers range_scan and
-// ranges_scan and the C entry points (host.h).  kh_trie_diff_host / kh_dev_trie_diff, the same
-// ordered frontier run over two tries in lockstep (diff.h: k_diff_*, diff_scan), and the batched
-// kh_trie_diffs_host / kh_dev_trie_diffs (k_diffs_*, diffs_scan) live here too.
+// their kernels (k_ranges_*: range.h holds the bodies of both); kh_trie_diff_host / kh_dev_trie_diff,
+// the same ordered frontier run over two tries in lockstep (diff.h: k_diff_*), and the batched
+// kh_trie_diffs_host / kh_dev_trie_diffs (k_diffs_*).  Every call launches kernels of its own; the
+// host code that sequences them is one driver: run_rounds (the round loop), fit_page (the tail) and
+// page_to_host / page_in_place (the two forms of an entry point), the 16 words they share named by
+// TotWord.  range_scan, ranges_scan, diff_scan and diffs_scan hold what differs: the workspace,
+// round 0 and the launches.  Then the C entry points (host.h).
 // A cold compilation unit of its own like prove_kernels.hip and load_kernels.hip: the hot kernels
 // of khst.hip keep their placement (tests/test_code_layout.py).
 #include <hip/hip_runtime.h>
@@ -351,446 +354,483 @@ __global__ void __launch_bounds__(BS) k_diffs_write(DSide A, DSide B, const uint
 }
 
 // ---------------------------------------------------------------------------
-// host: range scan (range.h)
+// host: the frontier driver the four services share (range.h, diff.h)
 // ---------------------------------------------------------------------------
-// what the rounds leave in the handle's gbuf for the write: the final frontier, the scanned value
-// offsets, the entries that fit
-struct RangePage {
-  const uint32_t* items = nullptr;
-  const uint64_t* pos = nullptr;
-  uint64_t k = 0, bytes = 0;
-  uint32_t rounds = 0;
+// The 16 device words every call keeps at `tot`; a round reads the first three back into
+// c->h_pinned, the tail all sixteen, at the same indices.
+enum TotWord : uint32_t {
+  T_NEXT = 0,    // the items of the next frontier (the total of the counts, before the cut)
+  T_EXPAND = 1,  // an item of this round has children to place (range), expanded or split (diff)
+  T_BAD = 2,     // a child a mask names is not in its side's map
+  T_STUB = 3,    // the lowest stub among the things looked at (k_*_lens), ~0: none
+  T_K = 4,       // k_*_fit: the things whose values fit val_cap,
+  T_BYTES = 5,   //   their bytes,
+  T_ALONE = 6,   //   the bytes of thing k alone, the first not returned,
+  T_REQ = 7,     //   its request (the batched calls),
+  T_KEY = 8,     //   and [8..12) its key
+  T_VALS = 12,   // the value bytes of all the things asked for (the total of the lengths)
+  T_ROOT = 15,   // round 0 of a diff: something to walk (k_diff_root), the live requests (k_diffs_root)
+  T_WORDS = 16,
 };
-static uint32_t g_range_rounds = 0;  // rounds of the last scan (khst_range_rounds: measurements only)
-extern "C" uint32_t khst_range_rounds() { return g_range_rounds; }
+// c->h_pinned past them, when a stub refuses the call: its node's hash, then its request
+enum PinWord : uint32_t { PIN_MISSING = 16, PIN_REQUEST = 20 };
 
-// The rounds of a range scan (range.h) and the fit to val_cap.  Two frontiers of max_entries + 2
-// items, one sync of a pinned word triple a round.  KH_OK with the page described in P (P.k = 0:
-// an empty answer) and *n_entries, *val_bytes, *more, next32 set; KH_ENOSPC with *val_bytes;
-// KH_ENODE with missing32.
-static int range_scan(kh_trie* h, uint32_t trie, const uint8_t* origin32, const uint8_t* limit32, uint64_t max_entries,
-                      uint64_t val_cap, RangePage& P, uint64_t* n_entries, uint64_t* val_bytes, int* more,
-                      uint8_t* next32, uint8_t* missing32) {
-  trie_settle(h);
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
+// a service's texts and its round cap (a sound trie of 64 nibbles ends well below it)
+struct Service {
+  const char* name;
+  uint32_t round_cap;
+  const char *enode, *enospc;
+};
+static const char ENOSPC_ENTRY[] = "value output too small for the first entry (*val_bytes holds its size)";
+static const char ENOSPC_DIFF[] = "value output too small for the first difference (*val_bytes holds its size)";
+static const Service RANGE = {
+    "range scan", 66, "the range meets a subtree the handle does not hold (missing32 names its node)", ENOSPC_ENTRY};
+static const Service RANGES = {"range scan", 66,
+                               "a range meets a subtree the handle does not hold (missing32 names its node, "
+                               "*n_done the request)",
+                               ENOSPC_ENTRY};
+static const Service DIFF = {
+    "trie diff", 68, "the diff meets a subtree a handle does not hold (missing32 names its node)", ENOSPC_DIFF};
+static const Service DIFFS = {"trie diff", 68,
+                              "a diff meets a subtree a handle does not hold (missing32 names its node, *n_done "
+                              "the request)",
+                              ENOSPC_DIFF};
+
+// the scratch every service carves out of its handle's gbuf beside its own frontier columns
+struct Work {
+  uint64_t* cnt = nullptr;            // a round's counts, then their scan; the tail's value offsets
+  char* scr = nullptr;                // the scratch of their scan
+  unsigned long long* tot = nullptr;  // TotWord
+  uint64_t F = 0;                     // the cut: no frontier grows past F items
+};
+// What the rounds and the tail leave for the write: the final frontier's columns (ia alone on a
+// range: its records; iq on the batched calls), the scanned value offsets, what fits.
+struct Page {
+  const uint32_t *ia = nullptr, *ib = nullptr, *iq = nullptr;
+  const uint64_t* pos = nullptr;
+  uint64_t nq = 0;            // the requests of a batched call (0: a single call)
+  uint64_t k = 0, bytes = 0;  // the things returned and their value bytes (k = 0: an empty answer)
+  uint64_t n1 = 0;            // the things looked at: k < n1 when the answer is cut
+  uint64_t req = 0;           // the cut request, or the refusing stub's; nq when every request is answered
+};
+struct PageOut {  // the caller's outputs every call has
+  uint64_t *n_entries, *val_bytes;
+  uint8_t *next32, *missing32;
+};
+struct Walk {
+  uint64_t ni = 0, visited = 0;  // the final frontier's items; the items selected in all rounds
+  uint32_t rounds = 0;
+  int cur = 0;  // the side of the two frontiers that holds the final one
+};
+
+static KeyRange key_range(const uint8_t* origin32, const uint8_t* limit32) {
   KeyRange g;
   memset(g.o, 0, 32);
   memset(g.l, 0xFF, 32);
   if (origin32) memcpy(g.o, origin32, 32);
   if (limit32) memcpy(g.l, limit32, 32);
+  return g;
+}
+
+// The rounds past round 0, from a frontier of ni items on side 0: select(cur, ni) launches the
+// count of the ni items on side cur, fill(cur, ni) places their children on side cur ^ 1.  One sync
+// of a pinned word triple a round; the round that expands nothing closes the walk.
+template <class Select, class Fill>
+static Walk run_rounds(kh_ctx* c, const Service& sv, const Work& w, uint64_t ni, Select select, Fill fill) {
+  hipStream_t st = c->st;
+  Walk r;
+  for (r.ni = ni; r.ni; ++r.rounds) {
+    if (r.rounds > sv.round_cap) throw KhError{KH_EINTERNAL, std::string(sv.name) + ": the rounds do not end"};
+    r.visited += r.ni;
+    HIPCHK(hipMemsetAsync(w.tot, 0, 16, st));  // T_NEXT, T_EXPAND
+    select(r.cur, r.ni);
+    LAUNCH_CHECK();
+    scan_u64(w.cnt, w.cnt, r.ni, (uint64_t*)(w.tot + T_NEXT), w.scr, st);
+    HIPCHK(hipMemcpyAsync(c->h_pinned, w.tot, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t total = c->h_pinned[T_NEXT], expand = c->h_pinned[T_EXPAND];
+    if (c->h_pinned[T_BAD]) throw KhError{KH_EINTERNAL, std::string(sv.name) + ": corrupt anchor map"};
+    const uint64_t nn = std::min(total, w.F);  // the cut
+    if (nn) {
+      fill(r.cur, r.ni);
+      LAUNCH_CHECK();
+    }
+    r.cur ^= 1;
+    r.ni = nn;
+    if (!expand) {
+      ++r.rounds;
+      break;
+    }
+  }
+  return r;
+}
+
+// After the rounds: the fit of the first me things of the final frontier (P.ia / ib / iq, P.pos
+// set by the caller) to val_cap.  lens(n1, nent) launches k_*_lens, fit(n1, nent) k_*_fit.  b is the
+// second handle of a diff (its stub word carries a side bit below the index), NULL on a range.
+// KH_OK with P.k, P.bytes, P.n1, P.req and *n_entries, *val_bytes, next32 set; KH_ENOSPC with
+// *val_bytes; KH_ENODE with missing32 and P.req.
+template <class Lens, class Fit>
+static int fit_page(kh_ctx* c, const Service& sv, const Work& w, uint64_t ni, uint64_t me, kh_trie* a, kh_trie* b,
+                    Page& P, const PageOut& o, Lens lens, Fit fit) {
+  hipStream_t st = c->st;
+  P.k = P.bytes = 0;
+  P.req = P.nq;
+  const uint64_t n1 = P.n1 = std::min(ni, me + 1), nent = std::min(ni, me);
+  if (n1 == 0) {
+    *o.n_entries = *o.val_bytes = 0;
+    return KH_OK;
+  }
+  HIPCHK(hipMemsetAsync(w.tot + T_STUB, 0xFF, 8, st));
+  lens(n1, nent);
+  LAUNCH_CHECK();
+  scan_u64(w.cnt, w.cnt, nent, (uint64_t*)(w.tot + T_VALS), w.scr, st);
+  fit(n1, nent);
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(c->h_pinned, w.tot, T_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (c->h_pinned[T_BAD]) throw KhError{KH_EINTERNAL, std::string(sv.name) + ": corrupt anchor map"};
+  const uint64_t stub = c->h_pinned[T_STUB];
+  if (stub != ~0ULL) {  // a missing subtree among the first max_entries + 1 things of the answer
+    const uint64_t r = (uint32_t)stub, at = stub >> (b ? 33 : 32);
+    kh_trie* of = (b && ((stub >> 32) & 1)) ? b : a;
+    HIPCHK(hipMemcpyAsync(c->h_pinned + PIN_MISSING, (const uint8_t*)of->recs.p + r * REC_BYTES + 96, 32,
+                          hipMemcpyDeviceToHost, st));
+    if (P.iq) HIPCHK(hipMemcpyAsync(c->h_pinned + PIN_REQUEST, P.iq + at, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (o.missing32) memcpy(o.missing32, c->h_pinned + PIN_MISSING, 32);
+    if (P.iq) P.req = (uint32_t)c->h_pinned[PIN_REQUEST];
+    return set_err(KH_ENODE, sv.enode);
+  }
+  const uint64_t k = c->h_pinned[T_K];
+  if (k == 0) {
+    *o.val_bytes = c->h_pinned[T_ALONE];
+    return set_err(KH_ENOSPC, sv.enospc);
+  }
+  P.k = k;
+  P.bytes = c->h_pinned[T_BYTES];
+  *o.n_entries = k;
+  *o.val_bytes = P.bytes;
+  if (k < n1) {
+    memcpy(o.next32, c->h_pinned + T_KEY, 32);
+    if (P.iq) P.req = c->h_pinned[T_REQ];
+  }
+  return KH_OK;
+}
+
+static DSide side_of(kh_trie* h) {
+  return DSide{recs_of(h), h->mcap ? map_of(h) : AMap{{nullptr}, {nullptr}, 0}, (const uint8_t*)h->heap.p};
+}
+
+// the page's keys, kinds (a diff), offsets, values and request offsets (a batched call) into device
+// buffers (P.k > 0): the one write kernel of the service, b NULL on a range
+static void page_write(kh_trie* a, kh_trie* b, const Page& P, uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals,
+                       uint64_t* d_voff, uint64_t* d_ent_off) {
+  hipStream_t st = a->c->st;
+  const dim3 grid = GRID(std::max(P.k, P.nq) + 1, BS);
+  if (!b && !P.iq)
+    hipLaunchKernelGGL(k_range_write, grid, dim3(BS), 0, st, recs_of(a), (const uint8_t*)a->heap.p, P.ia, P.k, P.pos,
+                       P.bytes, d_keys32, d_voff, d_vals);
+  else if (!b)
+    hipLaunchKernelGGL(k_ranges_write, grid, dim3(BS), 0, st, recs_of(a), (const uint8_t*)a->heap.p, P.ia, P.iq, P.k,
+                       P.pos, P.bytes, P.nq, d_keys32, d_voff, d_vals, d_ent_off);
+  else if (!P.iq)
+    hipLaunchKernelGGL(k_diff_write, grid, dim3(BS), 0, st, side_of(a), side_of(b), P.ia, P.ib, P.k, P.pos, P.bytes,
+                       d_keys32, d_kinds, d_voff, d_vals);
+  else
+    hipLaunchKernelGGL(k_diffs_write, grid, dim3(BS), 0, st, side_of(a), side_of(b), P.ia, P.ib, P.iq, P.k, P.pos,
+                       P.bytes, P.nq, d_keys32, d_kinds, d_voff, d_vals, d_ent_off);
+  LAUNCH_CHECK();
+}
+// The host form of a call, after its scan: the page written into a staging of its exact sizes and
+// copied to the caller's arrays (kinds on a diff, ent_off on a batched call, else NULL).
+static void page_to_host(kh_trie* a, kh_trie* b, const Page& P, uint8_t* keys32, uint8_t* kinds, uint8_t* vals,
+                         uint64_t* voff, uint64_t* ent_off) {
+  kh_ctx* c = a->c;
+  hipStream_t st = c->st;
+  if (P.k == 0) {
+    voff[0] = 0;
+    if (ent_off) memset(ent_off, 0, (P.nq + 1) * 8);
+    return;
+  }
+  if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
+  Layout Lo;
+  uint8_t *dk, *dkind = nullptr, *dv;
+  uint64_t *dvo, *deo = nullptr;
+  Lo.add(dk, P.k * 32 + 64);
+  Lo.add(dvo, P.k + 1);
+  if (ent_off) Lo.add(deo, P.nq + 1);
+  if (kinds) Lo.add(dkind, P.k + 64);
+  Lo.add(dv, P.bytes + 64);
+  place(c->out_emit, Lo);
+  page_write(a, b, P, dk, dkind, dv, dvo, deo);
+  HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
+  if (kinds) HIPCHK(hipMemcpyAsync(kinds, dkind, P.k, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (ent_off) HIPCHK(hipMemcpyAsync(ent_off, deo, (P.nq + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+}
+// the device form: the page written in place, or the offsets of an empty answer
+static void page_in_place(kh_trie* a, kh_trie* b, const Page& P, uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals,
+                          uint64_t* d_voff, uint64_t* d_ent_off) {
+  hipStream_t st = a->c->st;
+  if (P.k == 0) {
+    HIPCHK(hipMemsetAsync(d_voff, 0, 8, st));
+    if (d_ent_off) HIPCHK(hipMemsetAsync(d_ent_off, 0, (P.nq + 1) * 8, st));
+  } else {
+    if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
+    page_write(a, b, P, d_keys32, d_kinds, d_vals, d_voff, d_ent_off);
+  }
+  HIPCHK(hipStreamSynchronize(st));
+}
+// the request arrays of a batched host form into the context's in_keys: a trie id column per side
+// that needs one (pair: a diff, with a column for b), the origins and limits that are given
+struct Requests {
+  uint32_t *ta = nullptr, *tb = nullptr;
+  uint8_t *o = nullptr, *l = nullptr;
+};
+static void stage_requests(kh_ctx* c, Requests& d, uint64_t nq, const uint32_t* tries_a, bool want_a, bool pair,
+                           const uint32_t* tries_b, bool want_b, const uint8_t* origins32, const uint8_t* limits32) {
+  hipStream_t st = c->st;
+  Layout Li;
+  Li.add(d.ta, nq, want_a);
+  if (pair) Li.add(d.tb, nq, want_b);
+  Li.add(d.o, nq * 32, origins32 != nullptr);
+  Li.add(d.l, nq * 32, limits32 != nullptr);
+  place(c->in_keys, Li);
+  if (d.ta) HIPCHK(hipMemcpyAsync(d.ta, tries_a, nq * 4, hipMemcpyHostToDevice, st));
+  if (d.tb) HIPCHK(hipMemcpyAsync(d.tb, tries_b, nq * 4, hipMemcpyHostToDevice, st));
+  if (d.o) HIPCHK(hipMemcpyAsync(d.o, origins32, nq * 32, hipMemcpyHostToDevice, st));
+  if (d.l) HIPCHK(hipMemcpyAsync(d.l, limits32, nq * 32, hipMemcpyHostToDevice, st));
+}
+
+static bool refuse(const char* msg) {
+  set_err(KH_EINVAL, msg);
+  return false;
+}
+// the argument checks every call shares (ptrs: the handles and outputs it needs are there), then
+// what a pair of handles and a batch over a forest add
+static bool page_args_ok(bool ptrs, bool batched, uint64_t nq, uint64_t max_entries) {
+  if (!ptrs) return refuse("null handle or outputs");
+  if (!batched) return (max_entries != 0 && max_entries < (1ULL << 31)) || refuse("max_entries must be in [1, 2^31)");
+  return (nq != 0 && max_entries != 0 && nq < (1ULL << 31) && max_entries < (1ULL << 31) &&
+          nq + max_entries < (1ULL << 31)) ||
+         refuse("nq and max_entries must be at least 1 and nq + max_entries < 2^31");
+}
+static bool pair_ok(kh_trie* a, kh_trie* b) {
+  return a->c->dev == b->c->dev || refuse("the two handles live on different devices");
+}
+static bool ranges_ids_ok(kh_trie* h, const uint32_t* tries) {
+  return !(h->forest && !tries) || refuse("a forest needs a trie id per request");
+}
+static bool diffs_ids_ok(kh_trie* a, const uint32_t* tries_a, kh_trie* b, const uint32_t* tries_b) {
+  return !((a->forest && !tries_a) || (b->forest && !tries_b && !tries_a)) ||
+         refuse("a forest side needs a trie id per request");
+}
+
+// ---------------------------------------------------------------------------
+// host: range scan (range.h)
+// ---------------------------------------------------------------------------
+static uint32_t g_range_rounds = 0;  // rounds of the last scan (khst_range_rounds: measurements only)
+extern "C" uint32_t khst_range_rounds() { return g_range_rounds; }
+
+// A range scan (range.h) and the fit to val_cap: two frontiers of max_entries + 2 items.  KH_OK with
+// the page described in P (P.k = 0: an empty answer) and *n_entries, *val_bytes, *more, next32 set;
+// KH_ENOSPC with *val_bytes; KH_ENODE with missing32.
+static int range_scan(kh_trie* h, uint32_t trie, const uint8_t* origin32, const uint8_t* limit32, uint64_t max_entries,
+                      uint64_t val_cap, Page& P, const PageOut& o, int* more) {
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  const KeyRange g = key_range(origin32, limit32);
   const uint32_t t = h->forest ? trie : 0u;
   // (no more entries than records: the frontiers of a call asking for 2^31 - 1 stay the trie's size)
   const uint64_t me = std::min<uint64_t>(max_entries, std::max<uint64_t>(h->rn, 1));
-  const uint64_t F = me + 2;
   Layout L;
-  uint32_t *fa, *fb;
-  uint64_t* cnt;
-  unsigned long long* tot;
-  char* scr;
-  L.add(fa, F + 1);
-  L.add(fb, F + 1);
-  L.add(cnt, F + 1);
-  L.add(scr, scan_scratch_size(F + 1, 8));
-  L.add(tot, 16);
+  uint32_t* f[2];
+  Work w;
+  const uint64_t F = w.F = me + 2;
+  L.add(f[0], F + 1);
+  L.add(f[1], F + 1);
+  L.add(w.cnt, F + 1);
+  L.add(w.scr, scan_scratch_size(F + 1, 8));
+  L.add(w.tot, T_WORDS);
   place(h->gbuf, L);
-  uint64_t ni = 0;
-  uint32_t rounds = 0;
-  uint32_t *cur = fa, *nxt = fb;
-  if (h->rn && h->mcap && key_cmp(g.o, g.l) <= 0) {
-    const Recs R = recs_of(h);
-    const AMap M = map_of(h);
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
-    // (an empty trie, or an id the forest does not hold: the item is NONE and the first count drops it)
-    hipLaunchKernelGGL(k_range_root, dim3(1), dim3(1), 0, st, M, R, t, fa);
-    LAUNCH_CHECK();
-    for (ni = 1; ni; ++rounds) {
-      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
-      hipLaunchKernelGGL(k_range_count, GRID(ni, BS), dim3(BS), 0, st, R, g, cur, ni, cnt, tot + 1);
-      LAUNCH_CHECK();
-      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_range_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, g, cur, ni,
-                           (const uint64_t*)cnt, F, nxt, tot + 2);
-        LAUNCH_CHECK();
-      }
-      std::swap(cur, nxt);
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
-  }
-  P.rounds = g_range_rounds = rounds;
-  P.items = cur;
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *more = 0;
-    return KH_OK;
-  }
   const Recs R = recs_of(h);
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  hipLaunchKernelGGL(k_range_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, n1, (const uint64_t*)cnt, nent,
-                     (const uint64_t*)(tot + 12), val_cap, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things in range
-    const uint64_t r = (uint32_t)c->h_pinned[3];
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    return set_err(KH_ENODE, "the range meets a subtree the handle does not hold (missing32 names its node)");
+  Walk r;
+  if (h->rn && h->mcap && key_cmp(g.o, g.l) <= 0) {
+    const AMap M = map_of(h);
+    HIPCHK(hipMemsetAsync(w.tot, 0, T_WORDS * 8, st));
+    // (an empty trie, or an id the forest does not hold: the item is NONE and the first count drops it)
+    hipLaunchKernelGGL(k_range_root, dim3(1), dim3(1), 0, st, M, R, t, f[0]);
+    LAUNCH_CHECK();
+    r = run_rounds(
+        c, RANGE, w, 1,
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_range_count, GRID(ni, BS), dim3(BS), 0, st, R, g, f[cur], ni, w.cnt,
+                             w.tot + T_EXPAND);
+        },
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_range_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, g, f[cur], ni, w.cnt, F,
+                             f[cur ^ 1], w.tot + T_BAD);
+        });
   }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *more = k < n1;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the page's keys, offsets and values into device buffers (P.k > 0)
-static void range_emit(kh_trie* h, const RangePage& P, uint8_t* d_keys32, uint8_t* d_vals, uint64_t* d_voff) {
-  hipLaunchKernelGGL(k_range_write, GRID(P.k + 1, BS), dim3(BS), 0, h->c->st, recs_of(h), (const uint8_t*)h->heap.p,
-                     P.items, P.k, P.pos, P.bytes, d_keys32, d_voff, d_vals);
-  LAUNCH_CHECK();
-}
-static bool range_args_ok(kh_trie* h, uint64_t max_entries, const void* keys32, const void* voff,
-                          const uint64_t* n_entries, const uint64_t* val_bytes, const int* more, const uint8_t* next32) {
-  if (!h || !keys32 || !voff || !n_entries || !val_bytes || !more || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (max_entries == 0 || max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "max_entries must be in [1, 2^31)");
-    return false;
-  }
-  return true;
+  g_range_rounds = r.rounds;
+  P.ia = f[r.cur];
+  P.pos = w.cnt;
+  const int rc = fit_page(
+      c, RANGE, w, r.ni, me, h, nullptr, P, o,
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, P.ia, n1, nent, w.cnt, w.tot + T_STUB);
+      },
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_range_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, P.ia, n1, w.cnt, nent,
+                           (const uint64_t*)(w.tot + T_VALS), val_cap, w.tot + T_K, (uint64_t*)(w.tot + T_KEY));
+      });
+  if (rc == KH_OK) *more = P.k < P.n1;
+  return rc;
 }
 
 // ---- many ranges a call (range.h "MANY RANGES A CALL")
-// The rounds of nq range scans moving together and the fit to val_cap: the requests (device
-// arrays; d_tries NULL on a single trie, d_origins / d_limits nullable) through two segmented
-// frontiers of max_entries + 2 * nq items (range.h derives the cut), one sync of a pinned word
-// triple a round.  KH_OK with the answer described in P (P.k = 0: nothing in any range) and
-// *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with *val_bytes; KH_ENODE with missing32
-// and *n_done.
+// nq range scans moving together and the fit to val_cap: the requests (device arrays; d_tries NULL
+// on a single trie, d_origins / d_limits nullable) through two segmented frontiers of max_entries +
+// 2 * nq items (range.h derives the cut).  KH_OK with the answer described in P (P.k = 0: nothing in
+// any range) and *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with *val_bytes; KH_ENODE
+// with missing32 and *n_done.
 static int ranges_scan(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_origins, const uint8_t* d_limits,
-                       uint64_t nq, uint64_t max_entries, uint64_t val_cap, RangePage& P, const uint32_t*& P_iq,
-                       uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done, uint8_t* next32,
-                       uint8_t* missing32) {
+                       uint64_t nq, uint64_t max_entries, uint64_t val_cap, Page& P, const PageOut& o,
+                       uint64_t* n_done) {
   trie_settle(h);
   kh_ctx* c = h->c;
   hipStream_t st = c->st;
   // (a request returns no more entries than the handle has records: the frontiers of a call asking
   // for 2^31 - 1 follow the handle and nq)
   const uint64_t me = std::min<uint64_t>(max_entries, nq * std::max<uint64_t>(h->rn, 1));
-  const uint64_t F = me + 2 * nq;
   Layout L;
-  uint32_t *fa, *fb, *qa, *qb;
-  uint64_t* cnt;
-  unsigned long long* tot;
+  uint32_t *f[2], *fq[2];
+  Work w;
   KeyRange* G;
-  char* scr;
-  L.add(fa, F + 1);
-  L.add(fb, F + 1);
-  L.add(qa, F + 1);
-  L.add(qb, F + 1);
-  L.add(cnt, F + 1);
+  const uint64_t F = w.F = me + 2 * nq;
+  L.add(f[0], F + 1);
+  L.add(f[1], F + 1);
+  L.add(fq[0], F + 1);
+  L.add(fq[1], F + 1);
+  L.add(w.cnt, F + 1);
   L.add(G, nq);
-  L.add(scr, scan_scratch_size(F + 1, 8));
-  L.add(tot, 16);
+  L.add(w.scr, scan_scratch_size(F + 1, 8));
+  L.add(w.tot, T_WORDS);
   place(h->gbuf, L);
-  uint64_t ni = 0;
-  uint32_t rounds = 0;
-  uint32_t *cur = fa, *nxt = fb, *curq = qa, *nxtq = qb;
-  if (h->rn && h->mcap) {
-    const Recs R = recs_of(h);
-    const AMap M = map_of(h);
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
-    hipLaunchKernelGGL(k_ranges_root, GRID(nq, BS), dim3(BS), 0, st, M, R, d_tries, d_origins, d_limits, nq, G, fa, qa);
-    LAUNCH_CHECK();
-    for (ni = nq; ni; ++rounds) {
-      if (rounds > 66) throw KhError{KH_EINTERNAL, "range scan: the rounds do not end"};
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any branch among these
-      hipLaunchKernelGGL(k_ranges_count, GRID(ni, BS), dim3(BS), 0, st, R, (const KeyRange*)G, cur, curq, ni, cnt,
-                         tot + 1);
-      LAUNCH_CHECK();
-      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_ranges_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, (const KeyRange*)G, cur, curq,
-                           ni, (const uint64_t*)cnt, F, nxt, nxtq, tot + 2);
-        LAUNCH_CHECK();
-      }
-      std::swap(cur, nxt);
-      std::swap(curq, nxtq);
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
-  }
-  P.rounds = g_range_rounds = rounds;
-  P.items = cur;
-  P_iq = curq;
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *n_done = nq;
-    return KH_OK;
-  }
   const Recs R = recs_of(h);
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, cur, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  // fit: [4] k, [5] its bytes, [6] the length of entry k alone, [7] the request of thing k; [8..12) its key
-  hipLaunchKernelGGL(k_ranges_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, cur, curq, n1, (const uint64_t*)cnt, nent,
-                     (const uint64_t*)(tot + 12), val_cap, nq, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "range scan: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing subtree among the first max_entries + 1 things of the answer
-    const uint64_t r = (uint32_t)c->h_pinned[3], at = c->h_pinned[3] >> 32;
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)h->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 20, curq + at, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    *n_done = (uint32_t)c->h_pinned[20];
-    return set_err(KH_ENODE, "a range meets a subtree the handle does not hold (missing32 names its node, "
-                             "*n_done the request)");
+  Walk r;
+  if (h->rn && h->mcap) {
+    const AMap M = map_of(h);
+    HIPCHK(hipMemsetAsync(w.tot, 0, T_WORDS * 8, st));
+    hipLaunchKernelGGL(k_ranges_root, GRID(nq, BS), dim3(BS), 0, st, M, R, d_tries, d_origins, d_limits, nq, G, f[0],
+                       fq[0]);
+    LAUNCH_CHECK();
+    r = run_rounds(
+        c, RANGES, w, nq,
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_ranges_count, GRID(ni, BS), dim3(BS), 0, st, R, G, f[cur], fq[cur], ni, w.cnt,
+                             w.tot + T_EXPAND);
+        },
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_ranges_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, M, R, G, f[cur], fq[cur], ni,
+                             w.cnt, F, f[cur ^ 1], fq[cur ^ 1], w.tot + T_BAD);
+        });
   }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first entry (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *n_done = k < n1 ? c->h_pinned[7] : nq;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the answer's keys, value offsets, values and request offsets into device buffers (P.k > 0)
-static void ranges_emit(kh_trie* h, const RangePage& P, const uint32_t* iq, uint64_t nq, uint8_t* d_keys32,
-                        uint8_t* d_vals, uint64_t* d_voff, uint64_t* d_ent_off) {
-  hipLaunchKernelGGL(k_ranges_write, GRID(std::max(P.k, nq) + 1, BS), dim3(BS), 0, h->c->st, recs_of(h),
-                     (const uint8_t*)h->heap.p, P.items, iq, P.k, P.pos, P.bytes, nq, d_keys32, d_voff, d_vals,
-                     d_ent_off);
-  LAUNCH_CHECK();
-}
-static bool ranges_args_ok(kh_trie* h, const uint32_t* tries, uint64_t nq, uint64_t max_entries, const void* keys32,
-                           const void* voff, const void* ent_off, const uint64_t* n_entries, const uint64_t* val_bytes,
-                           const uint64_t* n_done, const uint8_t* next32) {
-  if (!h || !keys32 || !voff || !ent_off || !n_entries || !val_bytes || !n_done || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (nq == 0 || max_entries == 0 || nq >= (1ULL << 31) || max_entries >= (1ULL << 31) ||
-      nq + max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "nq and max_entries must be at least 1 and nq + max_entries < 2^31");
-    return false;
-  }
-  if (h->forest && !tries) {
-    set_err(KH_EINVAL, "a forest needs a trie id per request");
-    return false;
-  }
-  return true;
+  g_range_rounds = r.rounds;
+  P.ia = f[r.cur];
+  P.iq = fq[r.cur];
+  P.nq = nq;
+  P.pos = w.cnt;
+  const int rc = fit_page(
+      c, RANGES, w, r.ni, me, h, nullptr, P, o,
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_range_lens, GRID(n1, BS), dim3(BS), 0, st, R, P.ia, n1, nent, w.cnt, w.tot + T_STUB);
+      },
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_ranges_fit, GRID(nent + 1, BS), dim3(BS), 0, st, R, P.ia, P.iq, n1, w.cnt, nent,
+                           (const uint64_t*)(w.tot + T_VALS), val_cap, nq, w.tot + T_K, (uint64_t*)(w.tot + T_KEY));
+      });
+  if (rc != KH_ENOSPC) *n_done = P.req;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
 // host: trie diff (diff.h)
 // ---------------------------------------------------------------------------
-// what the rounds leave in a's gbuf for the write: the final frontier's two record columns, the
-// scanned value offsets, the differences that fit
-struct DiffPage {
-  const uint32_t *ia = nullptr, *ib = nullptr;
-  const uint64_t* pos = nullptr;
-  uint64_t k = 0, bytes = 0;
-};
 static uint32_t g_diff_rounds = 0;   // rounds of the last diff past the root pair, and the frontier
 static uint64_t g_diff_visited = 0;  // items it selected in them (khst_diff_*: measurements only)
 extern "C" uint32_t khst_diff_rounds() { return g_diff_rounds; }
 extern "C" uint64_t khst_diff_visited() { return g_diff_visited; }
 
-static DSide side_of(kh_trie* h) {
-  return DSide{recs_of(h), h->mcap ? map_of(h) : AMap{{nullptr}, {nullptr}, 0}, (const uint8_t*)h->heap.p};
-}
-
-// The rounds of a diff (diff.h) and the fit to val_cap, on a's stream with the scratch in a's gbuf
-// (both handles locked and settled by the caller, b's stream drained).  Two frontiers of
-// max_entries + 2 items, one sync of a pinned word triple a round.  KH_OK with the page described
-// in P (P.k = 0: no difference) and *n_entries, *val_bytes, *more, next32 set; KH_ENOSPC with
-// *val_bytes; KH_ENODE with missing32.
+// A diff (diff.h) and the fit to val_cap, on a's stream with the scratch in a's gbuf (both handles
+// locked and settled by the caller, b's stream drained): two frontiers of max_entries + 2 items.
+// KH_OK with the page described in P (P.k = 0: no difference) and *n_entries, *val_bytes, *more,
+// next32 set; KH_ENOSPC with *val_bytes; KH_ENODE with missing32.
 static int diff_scan(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b, const uint8_t* origin32,
-                     const uint8_t* limit32, uint64_t max_entries, uint64_t val_cap, DiffPage& P, uint64_t* n_entries,
-                     uint64_t* val_bytes, int* more, uint8_t* next32, uint8_t* missing32) {
+                     const uint8_t* limit32, uint64_t max_entries, uint64_t val_cap, Page& P, const PageOut& o,
+                     int* more) {
   kh_ctx* c = a->c;
   hipStream_t st = c->st;
-  KeyRange g;
-  memset(g.o, 0, 32);
-  memset(g.l, 0xFF, 32);
-  if (origin32) memcpy(g.o, origin32, 32);
-  if (limit32) memcpy(g.l, limit32, 32);
+  const KeyRange g = key_range(origin32, limit32);
   const uint32_t ta = a->forest ? trie_a : 0u, tb = b->forest ? trie_b : 0u;
   const bool has_a = a->rn && a->mcap, has_b = b->rn && b->mcap;
   // (no more differences than records: the frontiers of a call asking for 2^31 - 1 stay the tries' size)
   const uint64_t me = std::min<uint64_t>(max_entries, std::max<uint64_t>(a->rn + b->rn, 1));
-  const uint64_t F = me + 2;
   Layout L;
   uint32_t *fa[2], *fb[2], *fd[2], *sel;
-  uint64_t* cnt;
-  unsigned long long* tot;
-  char* scr;
+  Work w;
+  const uint64_t F = w.F = me + 2;
   for (int s = 0; s < 2; ++s) {
     L.add(fa[s], F + 1);
     L.add(fb[s], F + 1);
     L.add(fd[s], F + 1);
   }
   L.add(sel, F + 1);
-  L.add(cnt, F + 1);
-  L.add(scr, scan_scratch_size(F + 1, 8));
-  L.add(tot, 16);
+  L.add(w.cnt, F + 1);
+  L.add(w.scr, scan_scratch_size(F + 1, 8));
+  L.add(w.tot, T_WORDS);
   place(a->gbuf, L);
   const DSide A = side_of(a), B = side_of(b);
-  uint64_t ni = 0, visited = 0;
-  uint32_t rounds = 0;
-  int cur = 0;
+  Walk r;
   if ((has_a || has_b) && !(a == b && ta == tb) && key_cmp(g.o, g.l) <= 0) {
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
+    HIPCHK(hipMemsetAsync(w.tot, 0, T_WORDS * 8, st));
     hipLaunchKernelGGL(k_diff_root, dim3(1), dim3(1), 0, st, A, ta, (uint32_t)has_a, B, tb, (uint32_t)has_b, fa[0],
-                       fb[0], fd[0], tot + 15);
+                       fb[0], fd[0], w.tot + T_ROOT);
     LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, tot + 15, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pinned, w.tot + T_ROOT, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (ni = c->h_pinned[0]; ni; ++rounds) {
-      if (rounds > 68) throw KhError{KH_EINTERNAL, "trie diff: the rounds do not end"};
-      visited += ni;
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any item expanded or split
-      hipLaunchKernelGGL(k_diff_select, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, g, (const uint32_t*)fa[cur],
-                         (const uint32_t*)fb[cur], ni, sel, cnt, tot + 1);
-      LAUNCH_CHECK();
-      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "trie diff: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_diff_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, (const uint32_t*)fa[cur],
-                           (const uint32_t*)fb[cur], (const uint32_t*)fd[cur], (const uint32_t*)sel, ni,
-                           (const uint64_t*)cnt, F, fa[cur ^ 1], fb[cur ^ 1], fd[cur ^ 1], tot + 2);
-        LAUNCH_CHECK();
-      }
-      cur ^= 1;
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
+    r = run_rounds(
+        c, DIFF, w, c->h_pinned[0],
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_diff_select, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, g, fa[cur], fb[cur], ni,
+                             sel, w.cnt, w.tot + T_EXPAND);
+        },
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_diff_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, fa[cur], fb[cur], fd[cur],
+                             sel, ni, w.cnt, F, fa[cur ^ 1], fb[cur ^ 1], fd[cur ^ 1], w.tot + T_BAD);
+        });
   }
-  g_diff_rounds = rounds;
-  g_diff_visited = visited;
-  P.ia = fa[cur];
-  P.ib = fb[cur];
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *more = 0;
-    return KH_OK;
-  }
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_diff_lens, GRID(n1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  // fit: [4] k, [5] its bytes, [6] the bytes of difference k alone; [8..12) its key
-  hipLaunchKernelGGL(k_diff_fit, GRID(nent + 1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, (const uint64_t*)cnt, nent,
-                     (const uint64_t*)(tot + 12), val_cap, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "trie diff: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing thing among the first max_entries + 1 things in range
-    const uint64_t r = (uint32_t)c->h_pinned[3];
-    kh_trie* of = ((c->h_pinned[3] >> 32) & 1) ? b : a;
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)of->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    return set_err(KH_ENODE, "the diff meets a subtree a handle does not hold (missing32 names its node)");
-  }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first difference (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *more = k < n1;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the page's keys, kinds, offsets and values into device buffers (P.k > 0)
-static void diff_emit(kh_trie* a, kh_trie* b, const DiffPage& P, uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals,
-                      uint64_t* d_voff) {
-  hipLaunchKernelGGL(k_diff_write, GRID(P.k + 1, BS), dim3(BS), 0, a->c->st, side_of(a), side_of(b), P.ia, P.ib, P.k,
-                     P.pos, P.bytes, d_keys32, d_kinds, d_voff, d_vals);
-  LAUNCH_CHECK();
-}
-static bool diff_args_ok(kh_trie* a, kh_trie* b, uint64_t max_entries, const void* keys32, const void* kinds,
-                         const void* voff, const uint64_t* n_entries, const uint64_t* val_bytes, const int* more,
-                         const uint8_t* next32) {
-  if (!a || !b || !keys32 || !kinds || !voff || !n_entries || !val_bytes || !more || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (max_entries == 0 || max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "max_entries must be in [1, 2^31)");
-    return false;
-  }
-  if (a->c->dev != b->c->dev) {
-    set_err(KH_EINVAL, "the two handles live on different devices");
-    return false;
-  }
-  return true;
+  g_diff_rounds = r.rounds;
+  g_diff_visited = r.visited;
+  P.ia = fa[r.cur];
+  P.ib = fb[r.cur];
+  P.pos = w.cnt;
+  const int rc = fit_page(
+      c, DIFF, w, r.ni, me, a, b, P, o,
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diff_lens, GRID(n1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, nent, w.cnt,
+                           w.tot + T_STUB);
+      },
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diff_fit, GRID(nent + 1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, w.cnt, nent,
+                           (const uint64_t*)(w.tot + T_VALS), val_cap, w.tot + T_K, (uint64_t*)(w.tot + T_KEY));
+      });
+  if (rc == KH_OK) *more = P.k < P.n1;
+  return rc;
 }
 // both handles locked, settled and on a's device; b's work drained when it runs on another stream
 #define DIFF_ENTER(a, b)                                      \
@@ -806,30 +846,26 @@ static uint64_t g_diffs_visited = 0;  // frontier items it selected in them (khs
 extern "C" uint32_t khst_diffs_rounds() { return g_diffs_rounds; }
 extern "C" uint64_t khst_diffs_visited() { return g_diffs_visited; }
 
-// The rounds of nq diffs moving together and the fit to val_cap, on a's stream with the scratch in
-// a's gbuf (both handles locked and settled by the caller, b's stream drained): the requests (device
-// arrays; d_ta / d_tb NULL on a single trie, d_origins / d_limits nullable) through two segmented
-// frontiers of max_entries + 2 * nq items (diff.h derives the cut), one sync of the pinned words a
-// round.  KH_OK with the answer described in P and P_iq (P.k = 0: no difference in any request) and
-// *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with *val_bytes; KH_ENODE with missing32
-// and *n_done.
+// nq diffs moving together and the fit to val_cap, on a's stream with the scratch in a's gbuf (both
+// handles locked and settled by the caller, b's stream drained): the requests (device arrays; d_ta /
+// d_tb NULL on a single trie, d_origins / d_limits nullable) through two segmented frontiers of
+// max_entries + 2 * nq items (diff.h derives the cut).  KH_OK with the answer described in P (P.k =
+// 0: no difference in any request) and *n_entries, *val_bytes, *n_done, next32 set; KH_ENOSPC with
+// *val_bytes; KH_ENODE with missing32 and *n_done.
 static int diffs_scan(kh_trie* a, const uint32_t* d_ta, kh_trie* b, const uint32_t* d_tb, const uint8_t* d_origins,
-                      const uint8_t* d_limits, uint64_t nq, uint64_t max_entries, uint64_t val_cap, DiffPage& P,
-                      const uint32_t*& P_iq, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
-                      uint8_t* next32, uint8_t* missing32) {
+                      const uint8_t* d_limits, uint64_t nq, uint64_t max_entries, uint64_t val_cap, Page& P,
+                      const PageOut& o, uint64_t* n_done) {
   kh_ctx* c = a->c;
   hipStream_t st = c->st;
   const bool has_a = a->rn && a->mcap, has_b = b->rn && b->mcap;
   // (a request returns no more differences than the two handles have records: the frontiers of a
   // call asking for 2^31 - 1 follow the handles and nq)
   const uint64_t me = std::min<uint64_t>(max_entries, nq * std::max<uint64_t>(a->rn + b->rn, 1));
-  const uint64_t F = me + 2 * nq;
   Layout L;
   uint32_t *fa[2], *fb[2], *fd[2], *fq[2], *sel;
-  uint64_t* cnt;
-  unsigned long long* tot;
+  Work w;
   KeyRange* G;
-  char* scr;
+  const uint64_t F = w.F = me + 2 * nq;
   for (int s = 0; s < 2; ++s) {
     L.add(fa[s], F + 1);
     L.add(fb[s], F + 1);
@@ -837,130 +873,53 @@ static int diffs_scan(kh_trie* a, const uint32_t* d_ta, kh_trie* b, const uint32
     L.add(fq[s], F + 1);
   }
   L.add(sel, F + 1);
-  L.add(cnt, F + 1);
+  L.add(w.cnt, F + 1);
   L.add(G, nq);
-  L.add(scr, scan_scratch_size(F + 1, 8));
-  L.add(tot, 16);
+  L.add(w.scr, scan_scratch_size(F + 1, 8));
+  L.add(w.tot, T_WORDS);
   place(a->gbuf, L);
   const DSide A = side_of(a), B = side_of(b);
-  uint64_t ni = 0, visited = 0;
-  uint32_t rounds = 0;
-  int cur = 0;
+  Walk r;
   if (has_a || has_b) {
-    HIPCHK(hipMemsetAsync(tot, 0, 16 * 8, st));
+    HIPCHK(hipMemsetAsync(w.tot, 0, T_WORDS * 8, st));
     hipLaunchKernelGGL(k_diffs_root, GRID(nq, BS), dim3(BS), 0, st, A, d_ta, (uint32_t)has_a, B, d_tb, (uint32_t)has_b,
-                       (uint32_t)(a == b), d_origins, d_limits, nq, G, fa[0], fb[0], fd[0], fq[0], tot + 15);
+                       (uint32_t)(a == b), d_origins, d_limits, nq, G, fa[0], fb[0], fd[0], fq[0], w.tot + T_ROOT);
     LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, tot + 15, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_pinned, w.tot + T_ROOT, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const uint64_t live = c->h_pinned[0];  // (none: every request is empty or its roots are equal -- no round)
-    for (ni = live ? nq : 0; ni; ++rounds) {
-      if (rounds > 68) throw KhError{KH_EINTERNAL, "trie diff: the rounds do not end"};
-      visited += rounds ? ni : live;
-      HIPCHK(hipMemsetAsync(tot, 0, 16, st));  // [0] the items of the next frontier, [1] any item expanded or split
-      hipLaunchKernelGGL(k_diffs_select, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, (const KeyRange*)G,
-                         (const uint32_t*)fa[cur], (const uint32_t*)fb[cur], (const uint32_t*)fq[cur], ni, sel, cnt,
-                         tot + 1);
-      LAUNCH_CHECK();
-      scan_u64(cnt, cnt, ni, (uint64_t*)tot, scr, st);
-      HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 24, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      const uint64_t total = c->h_pinned[0], expand = c->h_pinned[1];
-      if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "trie diff: corrupt anchor map"};
-      const uint64_t nn = std::min(total, F);  // the cut
-      if (nn) {
-        hipLaunchKernelGGL(k_diffs_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, (const uint32_t*)fa[cur],
-                           (const uint32_t*)fb[cur], (const uint32_t*)fd[cur], (const uint32_t*)fq[cur],
-                           (const uint32_t*)sel, ni, (const uint64_t*)cnt, F, fa[cur ^ 1], fb[cur ^ 1], fd[cur ^ 1],
-                           fq[cur ^ 1], tot + 2);
-        LAUNCH_CHECK();
-      }
-      cur ^= 1;
-      ni = nn;
-      if (!expand) {
-        ++rounds;
-        break;
-      }
-    }
+    r = run_rounds(
+        c, DIFFS, w, live ? nq : 0,
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_diffs_select, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, G, fa[cur], fb[cur],
+                             fq[cur], ni, sel, w.cnt, w.tot + T_EXPAND);
+        },
+        [&](int cur, uint64_t ni) {
+          hipLaunchKernelGGL(k_diffs_fill, GRID(ni * EXP_LANES, BS), dim3(BS), 0, st, A, B, fa[cur], fb[cur], fd[cur],
+                             fq[cur], sel, ni, w.cnt, F, fa[cur ^ 1], fb[cur ^ 1], fd[cur ^ 1], fq[cur ^ 1],
+                             w.tot + T_BAD);
+        });
+    if (live) r.visited -= nq - live;  // (the first frontier holds every request; only the live ones are visited)
   }
-  g_diffs_rounds = rounds;
-  g_diffs_visited = visited;
-  P.ia = fa[cur];
-  P.ib = fb[cur];
-  P_iq = fq[cur];
-  P.pos = cnt;
-  P.k = P.bytes = 0;
-  const uint64_t n1 = std::min(ni, me + 1), nent = std::min(ni, me);
-  if (n1 == 0) {
-    *n_entries = *val_bytes = 0;
-    *n_done = nq;
-    return KH_OK;
-  }
-  HIPCHK(hipMemsetAsync(tot + 3, 0xFF, 8, st));
-  hipLaunchKernelGGL(k_diff_lens, GRID(n1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, nent, cnt, tot + 3);
-  LAUNCH_CHECK();
-  scan_u64(cnt, cnt, nent, (uint64_t*)(tot + 12), scr, st);
-  // fit: [4] k, [5] its bytes, [6] the bytes of difference k alone, [7] the request of thing k; [8..12) its key
-  hipLaunchKernelGGL(k_diffs_fit, GRID(nent + 1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, P_iq, n1, (const uint64_t*)cnt,
-                     nent, (const uint64_t*)(tot + 12), val_cap, nq, tot + 4, (uint64_t*)(tot + 8));
-  LAUNCH_CHECK();
-  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 16 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "trie diff: corrupt anchor map"};
-  if (c->h_pinned[3] != ~0ULL) {  // a missing thing among the first max_entries + 1 things of the answer
-    const uint64_t r = (uint32_t)c->h_pinned[3], at = c->h_pinned[3] >> 33;
-    kh_trie* of = ((c->h_pinned[3] >> 32) & 1) ? b : a;
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 16, (const uint8_t*)of->recs.p + r * REC_BYTES + 96, 32, hipMemcpyDeviceToHost,
-                          st));
-    HIPCHK(hipMemcpyAsync(c->h_pinned + 20, P_iq + at, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (missing32) memcpy(missing32, c->h_pinned + 16, 32);
-    *n_done = (uint32_t)c->h_pinned[20];
-    return set_err(KH_ENODE, "a diff meets a subtree a handle does not hold (missing32 names its node, *n_done "
-                             "the request)");
-  }
-  const uint64_t k = c->h_pinned[4];
-  if (k == 0) {
-    *val_bytes = c->h_pinned[6];
-    return set_err(KH_ENOSPC, "value output too small for the first difference (*val_bytes holds its size)");
-  }
-  P.k = k;
-  P.bytes = c->h_pinned[5];
-  *n_entries = k;
-  *val_bytes = P.bytes;
-  *n_done = k < n1 ? c->h_pinned[7] : nq;
-  if (k < n1) memcpy(next32, c->h_pinned + 8, 32);
-  return KH_OK;
-}
-// the answer's keys, kinds, value offsets, values and request offsets into device buffers (P.k > 0)
-static void diffs_emit(kh_trie* a, kh_trie* b, const DiffPage& P, const uint32_t* iq, uint64_t nq, uint8_t* d_keys32,
-                       uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff, uint64_t* d_ent_off) {
-  hipLaunchKernelGGL(k_diffs_write, GRID(std::max(P.k, nq) + 1, BS), dim3(BS), 0, a->c->st, side_of(a), side_of(b),
-                     P.ia, P.ib, iq, P.k, P.pos, P.bytes, nq, d_keys32, d_kinds, d_voff, d_vals, d_ent_off);
-  LAUNCH_CHECK();
-}
-static bool diffs_args_ok(kh_trie* a, const uint32_t* tries_a, kh_trie* b, const uint32_t* tries_b, uint64_t nq,
-                          uint64_t max_entries, const void* keys32, const void* kinds, const void* voff,
-                          const void* ent_off, const uint64_t* n_entries, const uint64_t* val_bytes,
-                          const uint64_t* n_done, const uint8_t* next32) {
-  if (!a || !b || !keys32 || !kinds || !voff || !ent_off || !n_entries || !val_bytes || !n_done || !next32) {
-    set_err(KH_EINVAL, "null handle or outputs");
-    return false;
-  }
-  if (nq == 0 || max_entries == 0 || nq >= (1ULL << 31) || max_entries >= (1ULL << 31) ||
-      nq + max_entries >= (1ULL << 31)) {
-    set_err(KH_EINVAL, "nq and max_entries must be at least 1 and nq + max_entries < 2^31");
-    return false;
-  }
-  if ((a->forest && !tries_a) || (b->forest && !tries_b && !tries_a)) {
-    set_err(KH_EINVAL, "a forest side needs a trie id per request");
-    return false;
-  }
-  if (a->c->dev != b->c->dev) {
-    set_err(KH_EINVAL, "the two handles live on different devices");
-    return false;
-  }
-  return true;
+  g_diffs_rounds = r.rounds;
+  g_diffs_visited = r.visited;
+  P.ia = fa[r.cur];
+  P.ib = fb[r.cur];
+  P.iq = fq[r.cur];
+  P.nq = nq;
+  P.pos = w.cnt;
+  const int rc = fit_page(
+      c, DIFFS, w, r.ni, me, a, b, P, o,
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diff_lens, GRID(n1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, nent, w.cnt,
+                           w.tot + T_STUB);
+      },
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diffs_fit, GRID(nent + 1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, P.iq, n1, w.cnt, nent,
+                           (const uint64_t*)(w.tot + T_VALS), val_cap, nq, w.tot + T_K, (uint64_t*)(w.tot + T_KEY));
+      });
+  if (rc != KH_ENOSPC) *n_done = P.req;
+  return rc;
 }
 
 extern "C" {
@@ -970,53 +929,21 @@ int kh_trie_diffs_host(kh_trie* a, const uint32_t* tries_a, kh_trie* b, const ui
                        uint64_t val_cap, uint8_t* keys32, uint8_t* kinds, uint8_t* vals, uint64_t* voff,
                        uint64_t* ent_off, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
                        uint8_t next32[32], uint8_t missing32[32]) {
-  if (!diffs_args_ok(a, tries_a, b, tries_b, nq, max_entries, keys32, kinds, voff, ent_off, n_entries, val_bytes,
-                     n_done, next32))
+  if (!page_args_ok(a && b && keys32 && kinds && voff && ent_off && n_entries && val_bytes && n_done && next32, true,
+                    nq, max_entries) ||
+      !diffs_ids_ok(a, tries_a, b, tries_b) || !pair_ok(a, b))
     return KH_EINVAL;
   API_TRY({
     DIFF_ENTER(a, b);
-    kh_ctx* c = a->c;
-    hipStream_t st = c->st;
     const bool own_b = b->forest && tries_b && tries_b != tries_a;  // (else b's ids are a's array)
-    Layout Li;
-    uint32_t *dta, *dtb;
-    uint8_t *dor, *dli;
-    Li.add(dta, nq, tries_a != nullptr && (a->forest || (b->forest && !own_b)));
-    Li.add(dtb, nq, own_b);
-    Li.add(dor, nq * 32, origins32 != nullptr);
-    Li.add(dli, nq * 32, limits32 != nullptr);
-    place(c->in_keys, Li);
-    if (dta) HIPCHK(hipMemcpyAsync(dta, tries_a, nq * 4, hipMemcpyHostToDevice, st));
-    if (dtb) HIPCHK(hipMemcpyAsync(dtb, tries_b, nq * 4, hipMemcpyHostToDevice, st));
-    if (dor) HIPCHK(hipMemcpyAsync(dor, origins32, nq * 32, hipMemcpyHostToDevice, st));
-    if (dli) HIPCHK(hipMemcpyAsync(dli, limits32, nq * 32, hipMemcpyHostToDevice, st));
-    DiffPage P;
-    const uint32_t* iq = nullptr;
-    const int rc = diffs_scan(a, a->forest ? dta : nullptr, b, b->forest ? (own_b ? dtb : dta) : nullptr, dor, dli, nq,
-                              max_entries, val_cap, P, iq, n_entries, val_bytes, n_done, next32, missing32);
+    Requests d;
+    stage_requests(a->c, d, nq, tries_a, tries_a != nullptr && (a->forest || (b->forest && !own_b)), true, tries_b,
+                   own_b, origins32, limits32);
+    Page P;
+    const int rc = diffs_scan(a, a->forest ? d.ta : nullptr, b, b->forest ? (own_b ? d.tb : d.ta) : nullptr, d.o, d.l,
+                              nq, max_entries, val_cap, P, {n_entries, val_bytes, next32, missing32}, n_done);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      voff[0] = 0;
-      memset(ent_off, 0, (nq + 1) * 8);
-      return KH_OK;
-    }
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dkind, *dv;
-    uint64_t *dvo, *deo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(deo, nq + 1);
-    Lo.add(dkind, P.k + 64);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    diffs_emit(a, b, P, iq, nq, dk, dkind, dv, dvo, deo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(kinds, dkind, P.k, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ent_off, deo, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    page_to_host(a, b, P, keys32, kinds, vals, voff, ent_off);
   })
 }
 
@@ -1025,27 +952,19 @@ int kh_dev_trie_diffs(kh_trie* a, const uint32_t* d_tries_a, kh_trie* b, const u
                       uint64_t val_cap, uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff,
                       uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
                       uint8_t next32[32], uint8_t missing32[32]) {
-  if (!diffs_args_ok(a, d_tries_a, b, d_tries_b, nq, max_entries, d_keys32, d_kinds, d_voff, d_ent_off, n_entries,
-                     val_bytes, n_done, next32))
+  if (!page_args_ok(a && b && d_keys32 && d_kinds && d_voff && d_ent_off && n_entries && val_bytes && n_done && next32,
+                    true, nq, max_entries) ||
+      !diffs_ids_ok(a, d_tries_a, b, d_tries_b) || !pair_ok(a, b))
     return KH_EINVAL;
   if ((((uintptr_t)d_voff) | ((uintptr_t)d_ent_off)) & 7) return set_err(KH_EINVAL, "voff and ent_off must be 8-byte aligned");
   API_TRY({
     DIFF_ENTER(a, b);
-    kh_ctx* c = a->c;
-    DiffPage P;
-    const uint32_t* iq = nullptr;
+    Page P;
     const int rc = diffs_scan(a, a->forest ? d_tries_a : nullptr, b,
                               b->forest ? (d_tries_b ? d_tries_b : d_tries_a) : nullptr, d_origins32, d_limits32, nq,
-                              max_entries, val_cap, P, iq, n_entries, val_bytes, n_done, next32, missing32);
+                              max_entries, val_cap, P, {n_entries, val_bytes, next32, missing32}, n_done);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-      HIPCHK(hipMemsetAsync(d_ent_off, 0, (nq + 1) * 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      diffs_emit(a, b, P, iq, nq, d_keys32, d_kinds, d_vals, d_voff, d_ent_off);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
+    page_in_place(a, b, P, d_keys32, d_kinds, d_vals, d_voff, d_ent_off);
   })
 }
 
@@ -1053,32 +972,17 @@ int kh_trie_diff_host(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b, 
                       const uint8_t limit32[32], uint64_t max_entries, uint64_t val_cap, uint8_t* keys32,
                       uint8_t* kinds, uint8_t* vals, uint64_t* voff, uint64_t* n_entries, uint64_t* val_bytes,
                       int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!diff_args_ok(a, b, max_entries, keys32, kinds, voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  if (!page_args_ok(a && b && keys32 && kinds && voff && n_entries && val_bytes && more && next32, false, 0,
+                    max_entries) ||
+      !pair_ok(a, b))
+    return KH_EINVAL;
   API_TRY({
     DIFF_ENTER(a, b);
-    kh_ctx* c = a->c;
-    hipStream_t st = c->st;
-    DiffPage P;
-    const int rc = diff_scan(a, trie_a, b, trie_b, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes,
-                             more, next32, missing32);
+    Page P;
+    const int rc = diff_scan(a, trie_a, b, trie_b, origin32, limit32, max_entries, val_cap, P,
+                             {n_entries, val_bytes, next32, missing32}, more);
     if (rc != KH_OK) return rc;
-    voff[0] = 0;
-    if (P.k == 0) return KH_OK;
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dkind, *dv;
-    uint64_t* dvo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(dkind, P.k + 64);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    diff_emit(a, b, P, dk, dkind, dv, dvo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(kinds, dkind, P.k, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    page_to_host(a, b, P, keys32, kinds, vals, voff, nullptr);
   })
 }
 
@@ -1086,22 +990,18 @@ int kh_dev_trie_diff(kh_trie* a, uint32_t trie_a, kh_trie* b, uint32_t trie_b, c
                      const uint8_t limit32[32], uint64_t max_entries, uint64_t val_cap, uint8_t* d_keys32,
                      uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff, uint64_t* n_entries, uint64_t* val_bytes,
                      int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!diff_args_ok(a, b, max_entries, d_keys32, d_kinds, d_voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  if (!page_args_ok(a && b && d_keys32 && d_kinds && d_voff && n_entries && val_bytes && more && next32, false, 0,
+                    max_entries) ||
+      !pair_ok(a, b))
+    return KH_EINVAL;
   if (((uintptr_t)d_voff) & 7) return set_err(KH_EINVAL, "voff must be 8-byte aligned");
   API_TRY({
     DIFF_ENTER(a, b);
-    kh_ctx* c = a->c;
-    DiffPage P;
-    const int rc = diff_scan(a, trie_a, b, trie_b, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes,
-                             more, next32, missing32);
+    Page P;
+    const int rc = diff_scan(a, trie_a, b, trie_b, origin32, limit32, max_entries, val_cap, P,
+                             {n_entries, val_bytes, next32, missing32}, more);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      diff_emit(a, b, P, d_keys32, d_kinds, d_vals, d_voff);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
+    page_in_place(a, b, P, d_keys32, d_kinds, d_vals, d_voff, nullptr);
   })
 }
 
@@ -1109,48 +1009,20 @@ int kh_trie_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* origin
                         uint64_t nq, uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap,
                         uint64_t* voff, uint64_t* ent_off, uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
                         uint8_t next32[32], uint8_t missing32[32]) {
-  if (!ranges_args_ok(h, tries, nq, max_entries, keys32, voff, ent_off, n_entries, val_bytes, n_done, next32))
+  if (!page_args_ok(h && keys32 && voff && ent_off && n_entries && val_bytes && n_done && next32, true, nq,
+                    max_entries) ||
+      !ranges_ids_ok(h, tries))
     return KH_EINVAL;
   API_TRY({
     HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    Layout Li;
-    uint32_t* dt;
-    uint8_t *dor, *dli;
-    Li.add(dt, nq, h->forest);
-    Li.add(dor, nq * 32, origins32 != nullptr);
-    Li.add(dli, nq * 32, limits32 != nullptr);
-    place(c->in_keys, Li);
-    if (dt) HIPCHK(hipMemcpyAsync(dt, tries, nq * 4, hipMemcpyHostToDevice, st));
-    if (dor) HIPCHK(hipMemcpyAsync(dor, origins32, nq * 32, hipMemcpyHostToDevice, st));
-    if (dli) HIPCHK(hipMemcpyAsync(dli, limits32, nq * 32, hipMemcpyHostToDevice, st));
-    RangePage P;
-    const uint32_t* iq = nullptr;
-    const int rc = ranges_scan(h, dt, dor, dli, nq, max_entries, val_cap, P, iq, n_entries, val_bytes, n_done, next32,
-                               missing32);
+    HIPCHK(hipSetDevice(h->c->dev));
+    Requests d;
+    stage_requests(h->c, d, nq, tries, h->forest, false, nullptr, false, origins32, limits32);
+    Page P;
+    const int rc = ranges_scan(h, d.ta, d.o, d.l, nq, max_entries, val_cap, P,
+                               {n_entries, val_bytes, next32, missing32}, n_done);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      voff[0] = 0;
-      memset(ent_off, 0, (nq + 1) * 8);
-      return KH_OK;
-    }
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dv;
-    uint64_t *dvo, *deo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(deo, nq + 1);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    ranges_emit(h, P, iq, nq, dk, dv, dvo, deo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(ent_off, deo, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    page_to_host(h, nullptr, P, keys32, nullptr, vals, voff, ent_off);
   })
 }
 
@@ -1158,80 +1030,53 @@ int kh_dev_trie_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_ori
                        uint64_t nq, uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap,
                        uint64_t* d_voff, uint64_t* d_ent_off, uint64_t* n_entries, uint64_t* val_bytes,
                        uint64_t* n_done, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!ranges_args_ok(h, d_tries, nq, max_entries, d_keys32, d_voff, d_ent_off, n_entries, val_bytes, n_done, next32))
+  if (!page_args_ok(h && d_keys32 && d_voff && d_ent_off && n_entries && val_bytes && n_done && next32, true, nq,
+                    max_entries) ||
+      !ranges_ids_ok(h, d_tries))
     return KH_EINVAL;
   if ((((uintptr_t)d_voff) | ((uintptr_t)d_ent_off)) & 7) return set_err(KH_EINVAL, "voff and ent_off must be 8-byte aligned");
   API_TRY({
     HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    RangePage P;
-    const uint32_t* iq = nullptr;
+    HIPCHK(hipSetDevice(h->c->dev));
+    Page P;
     const int rc = ranges_scan(h, h->forest ? d_tries : nullptr, d_origins32, d_limits32, nq, max_entries, val_cap, P,
-                               iq, n_entries, val_bytes, n_done, next32, missing32);
+                               {n_entries, val_bytes, next32, missing32}, n_done);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-      HIPCHK(hipMemsetAsync(d_ent_off, 0, (nq + 1) * 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      ranges_emit(h, P, iq, nq, d_keys32, d_vals, d_voff, d_ent_off);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
+    page_in_place(h, nullptr, P, d_keys32, nullptr, d_vals, d_voff, d_ent_off);
   })
 }
 
 int kh_trie_range_host(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
                        uint64_t max_entries, uint8_t* keys32, uint8_t* vals, uint64_t val_cap, uint64_t* voff,
                        uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!range_args_ok(h, max_entries, keys32, voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  if (!page_args_ok(h && keys32 && voff && n_entries && val_bytes && more && next32, false, 0, max_entries))
+    return KH_EINVAL;
   API_TRY({
     HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    hipStream_t st = c->st;
-    RangePage P;
-    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
-                              missing32);
+    HIPCHK(hipSetDevice(h->c->dev));
+    Page P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P,
+                              {n_entries, val_bytes, next32, missing32}, more);
     if (rc != KH_OK) return rc;
-    voff[0] = 0;
-    if (P.k == 0) return KH_OK;
-    if (P.bytes && !vals) throw KhError{KH_EINVAL, "null value buffer"};
-    Layout Lo;
-    uint8_t *dk, *dv;
-    uint64_t* dvo;
-    Lo.add(dk, P.k * 32 + 64);
-    Lo.add(dvo, P.k + 1);
-    Lo.add(dv, P.bytes + 64);
-    place(c->out_emit, Lo);
-    range_emit(h, P, dk, dv, dvo);
-    HIPCHK(hipMemcpyAsync(keys32, dk, P.k * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(voff, dvo, (P.k + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (P.bytes) HIPCHK(hipMemcpyAsync(vals, dv, P.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    page_to_host(h, nullptr, P, keys32, nullptr, vals, voff, nullptr);
   })
 }
 
 int kh_dev_trie_range(kh_trie* h, uint32_t trie, const uint8_t origin32[32], const uint8_t limit32[32],
                       uint64_t max_entries, uint8_t* d_keys32, uint8_t* d_vals, uint64_t val_cap, uint64_t* d_voff,
                       uint64_t* n_entries, uint64_t* val_bytes, int* more, uint8_t next32[32], uint8_t missing32[32]) {
-  if (!range_args_ok(h, max_entries, d_keys32, d_voff, n_entries, val_bytes, more, next32)) return KH_EINVAL;
+  if (!page_args_ok(h && d_keys32 && d_voff && n_entries && val_bytes && more && next32, false, 0, max_entries))
+    return KH_EINVAL;
   API_TRY({
     HANDLE_LOCK(h);
-    kh_ctx* c = h->c;
-    HIPCHK(hipSetDevice(c->dev));
-    RangePage P;
-    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P, n_entries, val_bytes, more, next32,
-                              missing32);
+    HIPCHK(hipSetDevice(h->c->dev));
+    Page P;
+    const int rc = range_scan(h, trie, origin32, limit32, max_entries, val_cap, P,
+                              {n_entries, val_bytes, next32, missing32}, more);
     if (rc != KH_OK) return rc;
-    if (P.k == 0) {
-      HIPCHK(hipMemsetAsync(d_voff, 0, 8, c->st));
-    } else {
-      if (P.bytes && !d_vals) throw KhError{KH_EINVAL, "null value buffer"};
-      range_emit(h, P, d_keys32, d_vals, d_voff);
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
+    page_in_place(h, nullptr, P, d_keys32, nullptr, d_vals, d_voff, nullptr);
   })
 }
 
 }  // extern "C"
+

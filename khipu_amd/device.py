@@ -580,47 +580,92 @@ def trie_range(h, origin=None, limit=None, max_entries=1024, val_cap=1 << 20, tr
     KH_ENOSPC (not even the first value fits) raises KhError with the size needed in .val_bytes;
     KH_ENODE (a partial handle: the page meets a missing subtree) raises MPTNodeMissingException
     with the hash to fetch in .missing."""
-    n = int(max_entries)
-    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
-    ob = np.frombuffer(origin, np.uint8).copy() if origin is not None else None
-    lb = np.frombuffer(limit, np.uint8).copy() if limit is not None else None
-    if (ob is not None and ob.size != 32) or (lb is not None and lb.size != 32):
+    ob, lb = _packed_keys32([origin], [limit])
+    o = _PageOut(max_entries, val_cap)
+    o.raise_for(lib().kh_trie_range_host(h, 0 if trie is None else trie, _at(ob), _at(lb), o.n, _at(o.keys),
+                                         _at(o.vals), o.val_cap, _at(o.voff), ctypes.byref(o.ne),
+                                         ctypes.byref(o.vb), ctypes.byref(o.more), _at(o.nxt), _at(o.miss)))
+    k = int(o.ne.value)
+    return ([o.keys[32 * i:32 * i + 32].tobytes() for i in range(k)],
+            [o.vals[int(o.voff[i]):int(o.voff[i + 1])].tobytes() for i in range(k)], bool(o.more.value),
+            o.nxt.tobytes() if o.more.value else None)
+
+
+def _at(x):
+    return x.ctypes.data if x is not None else None
+
+
+def _packed_keys32(origins, limits):
+    """The origins and the limits of the requests of a range or diff call, each packed into one
+    array of 32 bytes a request (None: the lowest / the highest key); None for a side no request gives."""
+    if any(x is not None and len(x) != 32 for x in (*origins, *limits)):
         raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
-    keys = np.zeros(32 * room, np.uint8)
-    vals = np.zeros(max(int(val_cap), 1), np.uint8)
-    voff = np.zeros(room + 1, np.uint64)
-    ne, vb, more = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
-    nxt = np.zeros(32, np.uint8)
-    miss = np.zeros(32, np.uint8)
-    rc = lib().kh_trie_range_host(h, 0 if trie is None else trie, ob.ctypes.data if ob is not None else None,
-                                  lb.ctypes.data if lb is not None else None, n, keys.ctypes.data, vals.ctypes.data,
-                                  int(val_cap), voff.ctypes.data, ctypes.byref(ne), ctypes.byref(vb),
-                                  ctypes.byref(more), nxt.ctypes.data, miss.ctypes.data)
-    if rc == _lib.KH_ENODE:
-        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
-        e.missing = miss.tobytes()
-        raise e
-    if rc == _lib.KH_ENOSPC:
-        e = _lib.KhError(rc, lib().kh_last_error().decode())
-        e.val_bytes = int(vb.value)
-        raise e
-    check(rc)
-    k = int(ne.value)
-    return ([keys[32 * i:32 * i + 32].tobytes() for i in range(k)],
-            [vals[int(voff[i]):int(voff[i + 1])].tobytes() for i in range(k)], bool(more.value),
-            nxt.tobytes() if more.value else None)
+
+    def pack(keys, absent):
+        if all(x is None for x in keys):
+            return None
+        return np.frombuffer(b"".join(bytes(x) if x is not None else absent for x in keys), np.uint8).copy()
+    return pack(origins, b"\0" * 32), pack(limits, b"\xff" * 32)
+
+
+class _PageOut:
+    """The outputs of one range or diff call (kinds: a diff; nq: the requests of a batched call, with
+    eoff and n_done, else more), and what its return code raises."""
+
+    def __init__(self, max_entries, val_cap, kinds=False, nq=None):
+        self.n, self.val_cap = int(max_entries), int(val_cap)
+        room = self.n if 0 < self.n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
+        self.keys = np.zeros(32 * room, np.uint8)
+        self.kinds = np.zeros(room, np.uint8) if kinds else None
+        self.vals = np.zeros(max(self.val_cap, 1), np.uint8)
+        self.voff = np.zeros(room + 1, np.uint64)
+        self.eoff = np.zeros(nq + 1, np.uint64) if nq is not None else None
+        self.ne, self.vb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.more, self.nd = ctypes.c_int(0), ctypes.c_uint64(0)
+        self.nxt = np.zeros(32, np.uint8)
+        self.miss = np.zeros(32, np.uint8)
+
+    def raise_for(self, rc):
+        if rc == _lib.KH_ENODE:
+            e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+            e.missing = self.miss.tobytes()
+            if self.eoff is not None:
+                e.request = int(self.nd.value)
+            raise e
+        if rc == _lib.KH_ENOSPC:
+            e = _lib.KhError(rc, lib().kh_last_error().decode())
+            e.val_bytes = int(self.vb.value)
+            raise e
+        check(rc)
+
+    def pages(self, entry):
+        """(pages, n_done, next) of a batched call: pages[q] = [entry(key, i, value)] over request q's
+        returned things i."""
+        nq = len(self.eoff) - 1
+        assert int(self.eoff[nq]) == int(self.ne.value)
+        kb, vbuf = self.keys[:32 * int(self.ne.value)].tobytes(), self.vals[:int(self.vb.value)].tobytes()
+        pages = [[entry(kb[32 * i:32 * i + 32], i, vbuf[int(self.voff[i]):int(self.voff[i + 1])])
+                  for i in range(int(self.eoff[q]), int(self.eoff[q + 1]))] for q in range(nq)]
+        done = int(self.nd.value)
+        return pages, done, self.nxt.tobytes() if done < nq else None
+
+
+def _grow_val_cap(call, val_cap):
+    """call(val_cap), again with val_cap grown while it raises KH_ENOSPC -> (its result, val_cap)"""
+    while True:
+        try:
+            return call(val_cap), val_cap
+        except _lib.KhError as e:
+            if e.code != _lib.KH_ENOSPC:
+                raise
+            val_cap = max(2 * val_cap, e.val_bytes)
 
 
 def _range_items(h, origin, limit, chunk, trie, val_cap=1 << 20):
     """Every (key, value) of [origin, limit] in key order, paged by next; val_cap grows on KH_ENOSPC."""
     while True:
-        try:
-            keys, vals, more, nxt = trie_range(h, origin, limit, chunk, val_cap, trie)
-        except _lib.KhError as e:
-            if e.code != _lib.KH_ENOSPC:
-                raise
-            val_cap = max(2 * val_cap, e.val_bytes)
-            continue
+        (keys, vals, more, nxt), val_cap = _grow_val_cap(
+            lambda cap: trie_range(h, origin, limit, chunk, cap, trie), val_cap)
         yield from zip(keys, vals)
         if not more:
             return
@@ -633,36 +678,25 @@ def trie_diff(ha, trie_a, hb, trie_b, origin=None, limit=None, max_entries=1024,
     KH_DIFF_ONLY_B or KH_DIFF_CHANGED with side b's value; next is the first differing key not
     returned when more.  Keys are trie keys.  KH_ENOSPC raises KhError with .val_bytes, KH_ENODE
     (partial handles) MPTNodeMissingException with the hash to fetch in .missing."""
-    n = int(max_entries)
-    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
-    ob = np.frombuffer(origin, np.uint8).copy() if origin is not None else None
-    lb = np.frombuffer(limit, np.uint8).copy() if limit is not None else None
-    if (ob is not None and ob.size != 32) or (lb is not None and lb.size != 32):
-        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
-    keys = np.zeros(32 * room, np.uint8)
-    kinds = np.zeros(room, np.uint8)
-    vals = np.zeros(max(int(val_cap), 1), np.uint8)
-    voff = np.zeros(room + 1, np.uint64)
-    ne, vb, more = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
-    nxt = np.zeros(32, np.uint8)
-    miss = np.zeros(32, np.uint8)
-    rc = lib().kh_trie_diff_host(ha, 0 if trie_a is None else trie_a, hb, 0 if trie_b is None else trie_b,
-                                 ob.ctypes.data if ob is not None else None,
-                                 lb.ctypes.data if lb is not None else None, n, int(val_cap), keys.ctypes.data,
-                                 kinds.ctypes.data, vals.ctypes.data, voff.ctypes.data, ctypes.byref(ne),
-                                 ctypes.byref(vb), ctypes.byref(more), nxt.ctypes.data, miss.ctypes.data)
-    if rc == _lib.KH_ENODE:
-        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
-        e.missing = miss.tobytes()
-        raise e
-    if rc == _lib.KH_ENOSPC:
-        e = _lib.KhError(rc, lib().kh_last_error().decode())
-        e.val_bytes = int(vb.value)
-        raise e
-    check(rc)
-    k = int(ne.value)
-    return ([(keys[32 * i:32 * i + 32].tobytes(), int(kinds[i]), vals[int(voff[i]):int(voff[i + 1])].tobytes())
-             for i in range(k)], bool(more.value), nxt.tobytes() if more.value else None)
+    ob, lb = _packed_keys32([origin], [limit])
+    o = _PageOut(max_entries, val_cap, kinds=True)
+    o.raise_for(lib().kh_trie_diff_host(ha, 0 if trie_a is None else trie_a, hb, 0 if trie_b is None else trie_b,
+                                        _at(ob), _at(lb), o.n, o.val_cap, _at(o.keys), _at(o.kinds), _at(o.vals),
+                                        _at(o.voff), ctypes.byref(o.ne), ctypes.byref(o.vb), ctypes.byref(o.more),
+                                        _at(o.nxt), _at(o.miss)))
+    k = int(o.ne.value)
+    return ([(o.keys[32 * i:32 * i + 32].tobytes(), int(o.kinds[i]),
+              o.vals[int(o.voff[i]):int(o.voff[i + 1])].tobytes()) for i in range(k)], bool(o.more.value),
+            o.nxt.tobytes() if o.more.value else None)
+
+
+def _add_changes(ents, ups, dels):
+    """the differences [(key, kind, value)] as upserts and deletes of the commit that brings a to b"""
+    for k, kind, v in ents:
+        if kind == _lib.KH_DIFF_ONLY_A:
+            dels.append(k)
+        else:
+            ups.append((k, v))
 
 
 def _diff_changes(ha, trie_a, hb, trie_b, chunk, val_cap=1 << 20):
@@ -670,18 +704,9 @@ def _diff_changes(ha, trie_a, hb, trie_b, chunk, val_cap=1 << 20):
     commit that brings side a to side b."""
     ups, dels, origin = [], [], None
     while True:
-        try:
-            ents, more, nxt = trie_diff(ha, trie_a, hb, trie_b, origin, None, chunk, val_cap)
-        except _lib.KhError as e:
-            if e.code != _lib.KH_ENOSPC:
-                raise
-            val_cap = max(2 * val_cap, e.val_bytes)
-            continue
-        for k, kind, v in ents:
-            if kind == _lib.KH_DIFF_ONLY_A:
-                dels.append(k)
-            else:
-                ups.append((k, v))
+        (ents, more, nxt), val_cap = _grow_val_cap(
+            lambda cap: trie_diff(ha, trie_a, hb, trie_b, origin, None, chunk, cap), val_cap)
+        _add_changes(ents, ups, dels)
         if not more:
             return ups, dels
         origin = nxt
@@ -704,49 +729,18 @@ def trie_diffs(ha, a_forest, hb, b_forest, requests, max_entries=1024, val_cap=1
     MPTNodeMissingException with the hash to fetch in .missing and the request in .request."""
     reqs = [tuple(q) for q in requests]
     nq = len(reqs)
-    n = int(max_entries)
-    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
-    if any(x is not None and len(x) != 32 for _, _, o, l in reqs for x in (o, l)):
-        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
     ta = tb = None
     if a_forest or b_forest:
         ta = np.asarray([t or 0 for t, _, _, _ in reqs] + [0], np.uint32)
     if b_forest and any(u is not None for _, u, _, _ in reqs):
         tb = np.asarray([(t or 0) if u is None else u for t, u, _, _ in reqs] + [0], np.uint32)
-    ob = lb = None
-    if any(o is not None for _, _, o, _ in reqs):
-        ob = np.frombuffer(b"".join(o if o is not None else b"\0" * 32 for _, _, o, _ in reqs), np.uint8).copy()
-    if any(l is not None for _, _, _, l in reqs):
-        lb = np.frombuffer(b"".join(l if l is not None else b"\xff" * 32 for _, _, _, l in reqs), np.uint8).copy()
-    keys = np.zeros(32 * room, np.uint8)
-    kinds = np.zeros(room, np.uint8)
-    vals = np.zeros(max(int(val_cap), 1), np.uint8)
-    voff = np.zeros(room + 1, np.uint64)
-    eoff = np.zeros(nq + 1, np.uint64)
-    ne, vb, nd = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    nxt = np.zeros(32, np.uint8)
-    miss = np.zeros(32, np.uint8)
-    ptr = lambda x: x.ctypes.data if x is not None else None  # noqa: E731
-    rc = lib().kh_trie_diffs_host(ha, ptr(ta), hb, ptr(tb), ptr(ob), ptr(lb), nq, n, int(val_cap), keys.ctypes.data,
-                                  kinds.ctypes.data, vals.ctypes.data, voff.ctypes.data, eoff.ctypes.data,
-                                  ctypes.byref(ne), ctypes.byref(vb), ctypes.byref(nd), nxt.ctypes.data,
-                                  miss.ctypes.data)
-    if rc == _lib.KH_ENODE:
-        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
-        e.missing = miss.tobytes()
-        e.request = int(nd.value)
-        raise e
-    if rc == _lib.KH_ENOSPC:
-        e = _lib.KhError(rc, lib().kh_last_error().decode())
-        e.val_bytes = int(vb.value)
-        raise e
-    check(rc)
-    assert int(eoff[nq]) == int(ne.value)
-    kb, vbuf = keys[:32 * int(ne.value)].tobytes(), vals[:int(vb.value)].tobytes()
-    pages = [[(kb[32 * i:32 * i + 32], int(kinds[i]), vbuf[int(voff[i]):int(voff[i + 1])])
-              for i in range(int(eoff[q]), int(eoff[q + 1]))] for q in range(nq)]
-    done = int(nd.value)
-    return pages, done, nxt.tobytes() if done < nq else None
+    ob, lb = _packed_keys32([o for _, _, o, _ in reqs], [l for _, _, _, l in reqs])
+    o = _PageOut(max_entries, val_cap, kinds=True, nq=nq)
+    o.raise_for(lib().kh_trie_diffs_host(ha, _at(ta), hb, _at(tb), _at(ob), _at(lb), nq, o.n, o.val_cap,
+                                         _at(o.keys), _at(o.kinds), _at(o.vals), _at(o.voff), _at(o.eoff),
+                                         ctypes.byref(o.ne), ctypes.byref(o.vb), ctypes.byref(o.nd), _at(o.nxt),
+                                         _at(o.miss)))
+    return o.pages(lambda key, i, value: (key, int(o.kinds[i]), value))
 
 
 def _diffs_changes(ha, a_forest, hb, b_forest, pairs, chunk, val_cap=1 << 20):
@@ -756,20 +750,10 @@ def _diffs_changes(ha, a_forest, hb, b_forest, pairs, chunk, val_cap=1 << 20):
     reqs = [(t, u, None, None) for t, u in pairs]
     first = 0  # the pair reqs[0] belongs to
     while reqs:
-        try:
-            pages, done, nxt = trie_diffs(ha, a_forest, hb, b_forest, reqs, chunk, val_cap)
-        except _lib.KhError as e:
-            if e.code != _lib.KH_ENOSPC:
-                raise
-            val_cap = max(2 * val_cap, e.val_bytes)
-            continue
+        (pages, done, nxt), val_cap = _grow_val_cap(
+            lambda cap: trie_diffs(ha, a_forest, hb, b_forest, reqs, chunk, cap), val_cap)
         for q, page in enumerate(pages[:done + 1]):
-            ups, dels = out[first + q]
-            for k, kind, v in page:
-                if kind == _lib.KH_DIFF_ONLY_A:
-                    dels.append(k)
-                else:
-                    ups.append((k, v))
+            _add_changes(page, *out[first + q])
         if done == len(reqs):
             break
         reqs = [(reqs[done][0], reqs[done][1], nxt, None)] + reqs[done + 1:]
@@ -805,45 +789,14 @@ def trie_ranges(h, requests, max_entries=1024, val_cap=1 << 20, forest=False):
     if not forest:
         reqs = [(0, o, l) for o, l in reqs]
     nq = len(reqs)
-    n = int(max_entries)
-    room = n if 0 < n < (1 << 31) else 1  # (else the call refuses with KH_EINVAL before it writes)
-    if any(x is not None and len(x) != 32 for _, o, l in reqs for x in (o, l)):
-        raise _lib.MPTException(_lib.KH_EINVAL, "origin and limit are 32-byte keys")
     tb = np.asarray([t for t, _, _ in reqs] + [0], np.uint32) if forest else None
-    ob = lb = None
-    if any(o is not None for _, o, _ in reqs):
-        ob = np.frombuffer(b"".join(o if o is not None else b"\0" * 32 for _, o, _ in reqs), np.uint8).copy()
-    if any(l is not None for _, _, l in reqs):
-        lb = np.frombuffer(b"".join(l if l is not None else b"\xff" * 32 for _, _, l in reqs), np.uint8).copy()
-    keys = np.zeros(32 * room, np.uint8)
-    vals = np.zeros(max(int(val_cap), 1), np.uint8)
-    voff = np.zeros(room + 1, np.uint64)
-    eoff = np.zeros(nq + 1, np.uint64)
-    ne, vb, nd = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    nxt = np.zeros(32, np.uint8)
-    miss = np.zeros(32, np.uint8)
-    rc = lib().kh_trie_ranges_host(h, tb.ctypes.data if tb is not None else None,
-                                   ob.ctypes.data if ob is not None else None,
-                                   lb.ctypes.data if lb is not None else None, nq, n, keys.ctypes.data,
-                                   vals.ctypes.data, int(val_cap), voff.ctypes.data, eoff.ctypes.data,
-                                   ctypes.byref(ne), ctypes.byref(vb), ctypes.byref(nd), nxt.ctypes.data,
-                                   miss.ctypes.data)
-    if rc == _lib.KH_ENODE:
-        e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
-        e.missing = miss.tobytes()
-        e.request = int(nd.value)
-        raise e
-    if rc == _lib.KH_ENOSPC:
-        e = _lib.KhError(rc, lib().kh_last_error().decode())
-        e.val_bytes = int(vb.value)
-        raise e
-    check(rc)
-    assert int(eoff[nq]) == int(ne.value)
-    kb, vbuf = keys[:32 * int(ne.value)].tobytes(), vals[:int(vb.value)].tobytes()
-    pages = [([kb[32 * i:32 * i + 32] for i in range(int(eoff[q]), int(eoff[q + 1]))],
-              [vbuf[int(voff[i]):int(voff[i + 1])] for i in range(int(eoff[q]), int(eoff[q + 1]))]) for q in range(nq)]
-    done = int(nd.value)
-    return pages, done, nxt.tobytes() if done < nq else None
+    ob, lb = _packed_keys32([o for _, o, _ in reqs], [l for _, _, l in reqs])
+    o = _PageOut(max_entries, val_cap, nq=nq)
+    o.raise_for(lib().kh_trie_ranges_host(h, _at(tb), _at(ob), _at(lb), nq, o.n, _at(o.keys), _at(o.vals),
+                                          o.val_cap, _at(o.voff), _at(o.eoff), ctypes.byref(o.ne),
+                                          ctypes.byref(o.vb), ctypes.byref(o.nd), _at(o.nxt), _at(o.miss)))
+    pages, done, nxt = o.pages(lambda key, i, value: (key, value))
+    return [([k for k, _ in p], [v for _, v in p]) for p in pages], done, nxt
 
 
 def _ranges_proof(h, requests, max_entries, val_cap, forest):

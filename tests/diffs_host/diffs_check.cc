@@ -18,8 +18,8 @@
 // The program builds every trie's records bottom-up (the builder of tests/host_common/replay.h),
 // puts them into ONE record store a side under their trie ids with one anchor map, prints
 //   T a|b id roothex
-// per trie, and replays every batch through diff.h's bodies as range_kernels.hip's diffs_scan and
-// k_diffs_* run them: round 0 one df_request a request, then per round select (16 lanes an item,
+// per trie, and replays every batch through diff.h's bodies as range_kernels.hip's frontier driver
+// (diffs_scan's launches in run_rounds and fit_page) and k_diffs_* run them: round 0 one df_request a request, then per round select (16 lanes an item,
 // each item against its own request's range), exclusive scan, the 16-lane fill into a next frontier
 // -- records, depths and requests -- of exactly the items it takes (never more than the cut), then
 // lengths, 64-bit scan, fit, and a write into outputs of exactly the scanned sizes: a write

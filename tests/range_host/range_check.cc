@@ -23,7 +23,7 @@
 
 #include "../../khipu_amd/csrc/range.h"
 
-// one range, as kh_trie_range_host runs it (range_kernels.hip range_scan / range_emit)
+// one range, as kh_trie_range_host runs it (range_kernels.hip range_scan / page_write)
 static void range(const Host& H, const Key& origin, const Key& limit, uint64_t max_entries, uint64_t val_cap,
                   uint64_t slack) {
   KeyRange g;

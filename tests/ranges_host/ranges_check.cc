@@ -16,8 +16,8 @@
 // The program builds every trie's records bottom-up (the builder of tests/host_common/replay.h),
 // puts them into ONE record store under their trie ids with one anchor map, prints
 //   T id roothex
-// per trie, and replays every batch through range.h's bodies as range_kernels.hip's ranges_scan
-// and k_ranges_* run them: the requests' KeyRanges into an nq-long array, round 0
+// per trie, and replays every batch through range.h's bodies as range_kernels.hip's frontier driver
+// (ranges_scan's launches in run_rounds and fit_page) and k_ranges_* run them: the requests' KeyRanges into an nq-long array, round 0
 // one map_find a request, then count, exclusive scan and the 16-lane fill into a next frontier --
 // records and requests -- of exactly the items it takes (never more than the cut), then lengths,
 // 64-bit scan, fit, and a write into outputs of exactly the scanned sizes: a write anywhere else

@@ -243,6 +243,33 @@ def test_single_trie_handle_copy_compact(khst, oracle):
         h.close()
 
 
+def test_single_and_batched_calls_report_the_same_rounds(khst, oracle):
+    """khst_range_rounds after a single call and after the one-request batch of it (the two share
+    the round loop that counts): none on an empty trie, one on a one-key trie (the root item is a
+    leaf: the first round closes the walk), and equal on the 2,000-entry trie, with equal entries."""
+    from khipu_amd._lib import lib
+    from khipu_amd.device import Ctx, ResidentTrie
+    rounds = lib().khst_range_rounds
+    rounds.restype = ctypes.c_uint32
+    r = random.Random(73)
+    key, val = C._rk(r), C.account_value(r)
+    for t, want, entries in ((ResidentTrie(Ctx(0), [], [], emit=False), 0, ([], [])),
+                             (ResidentTrie(Ctx(0), [key], [val], emit=False), 1, ([key], [val]))):
+        assert t.range()[:2] == entries and rounds() == want
+        assert t.ranges([(None, None)]) == ([entries], 1, None) and rounds() == want
+        t.close()
+    tries, content, _, _ = _state(oracle, "big")
+    ks = [k for k, _ in content[5]]
+    assert len(ks) == 2000
+    f = _load(tries)
+    for o, l, mx in ((None, None, 3000), (None, None, 700), (ks[300], ks[1500], 500), (ks[1999], None, 10)):
+        keys, vals, more, nxt = f.range(5, o, l, mx, BC.BIG)
+        single = rounds()
+        assert f.ranges([(5, o, l)], mx, BC.BIG) == ([(keys, vals)], 0 if more else 1, nxt), (o, l, mx)
+        assert rounds() == single and 0 < single <= 66 and keys, (o, l, mx)
+    f.close()
+
+
 def test_partial_forest(khst, oracle):
     """A partial forest refuses with the hash AND the request the reference's walk over the held
     nodes names, answers the batches that end before a missing subtree, and a fetch loop from
