@@ -489,6 +489,40 @@ int kh_forest_roots(kh_trie* f, uint32_t* h_tries, uint8_t* h_roots32, uint64_t 
  * untouched; export cursors end.  KH_EINVAL while a savepoint is open, as for kh_trie_compact. */
 int kh_forest_evict(kh_trie* f, const uint32_t* tries, uint64_t k, uint64_t* n_evicted);
 
+/* Subtrees of a resident trie back to stubs, by nibble path: the inverse of kh_trie_fill_nodes, and
+ * the way a working set shrinks inside one large trie.  All arrays are host arrays.  Prefix i is the
+ * first depths[i] nibbles of paths32[32i..) (two nibbles a byte, high nibble first; nibbles past the
+ * depth are ignored) in trie tries[i] (a forest; ignored and nullable on a single trie).  It names
+ * the subtree that HANGS there: the node the slot of a branch, depths[i] nibbles down, refers to -- a
+ * leaf, a branch, or an extension with its branch.  The path of a branch under an extension is not
+ * where a subtree hangs (the extension's path is): it reports NONE.
+ *   KH_EVICT_DONE      the node there was referenced by hash: every record below it dies (stubs
+ *                      among them too, their values become dead heap) and its own record becomes
+ *                      the plain stub a partial load would have left; hashes32[32i..) is that hash
+ *   KH_EVICT_STUB      already a stub, of either form: nothing changes; hashes32 = the hash it asks for
+ *   KH_EVICT_EMBEDDED  the node there is embedded in its parent (< 32 B): never a stub; hash zero
+ *   KH_EVICT_NONE      an empty slot, inside or off a leaf's or extension's path, below a leaf, below
+ *                      a stub, or a trie the handle does not hold; hash zero
+ * Afterwards the handle answers every call as kh_trie_open_partial / kh_forest_load_partial would
+ * from a store lacking exactly those subtrees' nodes (record order apart): the root, the last
+ * commit's roots and the write-back set do not change, reads answer KH_FOUND_UNKNOWN or KH_ENODE
+ * with the hash, a commit that reaches the stub is refused with it, kh_trie_fill_nodes brings the
+ * subtree back and kh_trie_compact reclaims the space.  kh_trie_size falls by the keys evicted and
+ * kh_trie_stubs stays exact.  Nullable outputs: *n_evicted the DONE prefixes, *n_keys the keys
+ * evicted, *n_records the records that died (those below the anchors; an anchor's own record is
+ * rewritten in place).  Export cursors end.
+ * KH_EINVAL, with the handle exactly as before: a null handle or array, tries NULL on a forest, a
+ * depth of 0 (a root is never a stub) or above 64, n >= 2^31, two listed prefixes of one trie where
+ * one equals or extends the other, a savepoint open.  n == 0 is KH_OK and does nothing.  The cost
+ * follows the handle's records, as kh_forest_evict's: one 64-byte line a record. */
+#define KH_EVICT_NONE 0
+#define KH_EVICT_DONE 1
+#define KH_EVICT_STUB 2
+#define KH_EVICT_EMBEDDED 3
+int kh_trie_evict_subtrees(kh_trie* h, const uint32_t* tries, const uint8_t* paths32, const uint8_t* depths,
+                           uint64_t n, uint8_t* status, uint8_t* hashes32,
+                           uint64_t* n_evicted, uint64_t* n_keys, uint64_t* n_records);
+
 /* One block (BlockWorldState.flush, BlockWorldState.scala:243-252 then TrieAccounts.flush):
  * the storage ops into the forest, each touched trie's new root written into the stateRoot
  * field of the account upserts that name it (d_a_up_trie[i], KH_NO_TRIE for none; the body

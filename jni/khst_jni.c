@@ -1055,6 +1055,42 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_forestEvict(JNIEnv* env, jclass
   return (jlong)dropped;
 }
 
+/* subtrees of a resident trie back to stubs (kh_trie_evict_subtrees): one prefix per byte of depths,
+ * the first depths[i] nibbles of paths32[32i..) in trie tries[i] (nullable on a single trie); status
+ * (one byte a prefix, KH_EVICT_*) and hashes32 (32 bytes a prefix: the hash to fetch to bring the
+ * subtree back) are filled; returns the keys evicted.  Region copies: the call runs kernels. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_evictSubtrees(JNIEnv* env, jclass cls, jlong handle, jintArray tries,
+                                                              jbyteArray paths32, jbyteArray depths, jbyteArray status,
+                                                              jbyteArray hashes32) {
+  (void)cls;
+  const uint64_t n = (uint64_t)len_of(env, depths);
+  if ((uint64_t)len_of(env, paths32) < 32 * n || (tries && (uint64_t)len_of(env, tries) < n) ||
+      (uint64_t)len_of(env, status) < n || (uint64_t)len_of(env, hashes32) < 32 * n) {
+    throw_cls(env, "java/lang/IllegalArgumentException",
+              "paths32 / hashes32: 32 bytes a prefix; tries / status: one entry a prefix");
+    return 0;
+  }
+  uint64_t keys = 0;
+  Bufs b = {0};
+  const uint32_t* t = in_i(env, &b, tries);
+  const uint8_t* p = in_b(env, &b, paths32);
+  const uint8_t* d = in_b(env, &b, depths);
+  uint8_t* st = bufs_alloc(&b, (size_t)(n ? n : 1));
+  uint8_t* hs = bufs_alloc(&b, 32 * (size_t)(n ? n : 1));
+  if (bufs_failed(env, &b)) return 0;
+  const int rc = kh_trie_evict_subtrees(H(handle), t, p, d, n, st, hs, NULL, &keys, NULL);
+  if (rc == KH_OK) {
+    put_b(env, status, st, n);
+    put_b(env, hashes32, hs, 32 * n);
+  }
+  bufs_free(&b);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)keys;
+}
+
 /* One block (BlockWorldState.scala:243-252 then TrieAccounts.flush): storage ops into the
  * forest, the new storage roots written into the named account bodies (accTrie[i], -1 =
  * KH_NO_TRIE: none), the account ops into the state trie.  All or nothing.  Returns the state

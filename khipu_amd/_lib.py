@@ -44,6 +44,12 @@ KH_RANGE_BAD_NODE = 3    # a node met on a boundary path is not a well-formed tr
 KH_RANGE_BAD_ROOT = 4    # the rebuilt root differs from the given one
 KH_RANGE_INCOMPLETE = 5  # no entries, yet the proof shows a key at or after origin
 
+# kh_trie_evict_subtrees: status per prefix
+KH_EVICT_NONE = 0      # no subtree hangs there in what the handle holds
+KH_EVICT_DONE = 1      # evicted: the hash is the one to fetch to bring it back
+KH_EVICT_STUB = 2      # already a stub there: the hash it asks for
+KH_EVICT_EMBEDDED = 3  # the node there is embedded in its parent (< 32 B): never a stub
+
 # every symbol include/khst.h declares
 EXPORTS = (
     "kh_last_error", "kh_version", "kh_device_count", "kh_kec256_batch", "kh_trie_root",
@@ -62,7 +68,7 @@ EXPORTS = (
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
     "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
-    "kh_trie_diffs_host", "kh_dev_trie_diffs",
+    "kh_trie_diffs_host", "kh_dev_trie_diffs", "kh_trie_evict_subtrees",
 )
 
 
@@ -197,6 +203,7 @@ def lib():
     L.kh_forest_load_nodes_host.argtypes = L.kh_forest_load_nodes.argtypes
     L.kh_forest_roots.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.kh_forest_evict.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+    L.kh_trie_evict_subtrees.argtypes = [vp, vp, vp, vp, u64, vp, vp] + [ctypes.POINTER(u64)] * 3
     L.kh_trie_open_partial.argtypes = L.kh_trie_open_nodes.argtypes
     L.kh_trie_open_partial_host.argtypes = L.kh_trie_open_nodes_host.argtypes
     L.kh_forest_load_partial.argtypes = L.kh_forest_load_nodes.argtypes

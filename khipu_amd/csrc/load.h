@@ -332,4 +332,88 @@ KH_HD bool load_in_list(const Recs& R, uint64_t r, const uint32_t* tries, uint32
 KH_HD bool load_holds_key(const Recs& R, uint64_t r) { return R.rdb[r] == EL_LEAF || R.rdb[r] == VB_DEPTH; }
 KH_HD bool load_is_stub(const Recs& R, uint64_t r) { return R.rlive[r] == REC_LIVE && R.rdb[r] == EL_STUB; }
 
+// ---- kh_trie_evict_subtrees: the inverse of the fill.  A prefix (trie, p nibbles) names the
+// subtree that hangs there: the live record anchored at exactly (trie, p, prefix).
+//   probe  one map_find a prefix: status, the hash to fetch, the record;
+//   flag   one streaming pass over the records (their first line): a record dies iff an evicted
+//          prefix of its trie is a proper prefix of its anchor path;
+//   stub   the anchors' records rewritten in place as plain stubs (the anchor tag and map_find's
+//          check read only the first p nibbles, so the record keeps its map slot).
+constexpr uint8_t EVICT_NONE = 0, EVICT_DONE = 1, EVICT_STUB = 2, EVICT_EMBEDDED = 3;  // (khst.h KH_EVICT_*)
+// the evicted prefixes, sorted by (trie, zero-padded path), none equal to or extending another
+struct EvictList {
+  const uint32_t* trie;
+  const uint64_t* path;  // [m*4] zero past the depth
+  const uint8_t* depth;
+  uint64_t m;
+};
+
+// prefix (t, p, P): its status; *rec the record found there (NONE: none), hash the one to fetch
+// (zero for NONE and EMBEDDED), *is_key: the record holds one of the trie's keys
+KH_HD uint8_t evict_probe(const AMap& M, const Recs& R, uint32_t t, uint32_t p, const uint64_t* P, uint32_t* rec,
+                          uint64_t hash[4], uint8_t* is_key) {
+  for (int q = 0; q < 4; ++q) hash[q] = 0;
+  *is_key = 0;
+  const uint32_t r = map_find(M, R, t, p, P);
+  *rec = r;
+  if (r == NONE || R.rlive[r] != REC_LIVE) {
+    *rec = NONE;
+    return EVICT_NONE;
+  }
+  if (R.rdb[r] == EL_STUB) {
+    for (int q = 0; q < 4; ++q) hash[q] = R.rbref[4ull * r + q];
+    return EVICT_STUB;
+  }
+  if (R.rrl[r] < 32) return EVICT_EMBEDDED;
+  for (int q = 0; q < 4; ++q) hash[q] = R.rref[4ull * r + q];
+  *is_key = load_holds_key(R, r) ? 1 : 0;
+  return EVICT_DONE;
+}
+
+// the last entry of E not after (t, K) in (trie, path) order, plus one (0: none)
+KH_HD uint64_t evict_upper_bound(const EvictList& E, uint32_t t, const uint64_t* K) {
+  uint64_t lo = 0, hi = E.m;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    const uint32_t mt = E.trie[mid];
+    const int c = mt != t ? (mt < t ? -1 : 1) : key_cmp(E.path + 4 * mid, K);
+    if (c <= 0)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+// does live record r lie strictly below an evicted prefix?  Every key between a zero-padded prefix
+// and a key that starts with it starts with it too, and no listed prefix extends another: so the
+// only candidate is the predecessor of the record's key in the sorted list.
+KH_HD bool evict_covers(const Recs& R, uint64_t r, const EvictList& E) {
+  if (R.rlive[r] != REC_LIVE) return false;
+  const uint64_t* K = R.key(r);
+  const uint32_t t = R.rt[r];
+  const uint64_t u = evict_upper_bound(E, t, K);
+  if (u == 0) return false;
+  const uint64_t i = u - 1;
+  return E.trie[i] == t && E.depth[i] < R.rd[r] && prefix_eq(E.path + 4 * i, K, E.depth[i]);
+}
+// record r, anchored at depth p, becomes the plain stub that stands for it: what a partial load
+// leaves for a hash the store lacks (load_stub_record with the item's d == a)
+KH_HD void evict_stub_record(const Recs& R, uint64_t r, uint32_t p) {
+  RecVal v;
+  for (int q = 0; q < 4; ++q) {
+    v.k[q] = prefix_word(R.key(r), p, q);
+    v.ref[q] = v.bref[q] = R.rref[4 * r + q];
+  }
+  v.t = R.rt[r];
+  v.d = (uint8_t)p;
+  v.db = EL_STUB;
+  v.mask = (uint16_t)p;
+  v.live = REC_LIVE;
+  v.rl = 32;
+  v.brl = 32;
+  v.vl = 0;
+  v.vo = 0;
+  rec_store(R.rk.b, r, v);
+}
+
 }  // namespace khst

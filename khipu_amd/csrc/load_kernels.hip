@@ -9,6 +9,7 @@
 
 #include "load.h"
 #include "host.h"
+#include "wave.h"
 
 using namespace khst;
 
@@ -121,6 +122,39 @@ __global__ void __launch_bounds__(BS) k_evict_list(uint64_t n, const uint32_t* f
   const uint64_t r = (uint64_t)blockIdx.x * BS + threadIdx.x;
   if (r >= n || !flag[r]) return;
   if (pos[r] < cap) list[pos[r]] = (uint32_t)r;
+}
+
+// kh_trie_evict_subtrees (load.h): the probe, one thread a listed prefix ...
+__global__ void __launch_bounds__(BS) k_evsub_probe(AMap M, Recs R, EvictList P, uint8_t* status, uint64_t* hash,
+                                                    uint32_t* rec, uint8_t* is_key) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i >= P.m) return;
+  uint64_t h[4];
+  status[i] = evict_probe(M, R, P.trie[i], P.depth[i], P.path + 4 * i, rec + i, h, is_key + i);
+  for (int q = 0; q < 4; ++q) hash[4 * i + q] = h[q];
+}
+// ... the flags of the records below an evicted prefix, one thread a record reading its first line
+// (cnt[0]: those holding a key, cnt[1]: the stubs; a wave reduction and one atomic a wave; the list
+// comes from the flags' scan through k_evict_list) ...
+__global__ void __launch_bounds__(BS) k_evsub_flags(Recs R, uint64_t n, EvictList E, uint32_t* flag,
+                                                    unsigned long long* cnt) {
+  const uint64_t r = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  const bool in = r < n && evict_covers(R, r, E);
+  if (r < n) flag[r] = in ? 1u : 0u;
+  unsigned long long keys = (in && load_holds_key(R, r)) ? 1 : 0, stubs = (in && R.rdb[r] == EL_STUB) ? 1 : 0;
+  keys = wave_sum(keys);
+  stubs = wave_sum(stubs);
+  if ((threadIdx.x & 63) == 0) {
+    if (keys) atomicAdd(cnt, keys);
+    if (stubs) atomicAdd(cnt + 1, stubs);
+  }
+}
+// ... and the anchors' records rewritten as stubs
+__global__ void __launch_bounds__(BS) k_evsub_stub(Recs R, const uint32_t* rec, const uint8_t* depth, uint64_t m,
+                                                   uint64_t rn) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i >= m || rec[i] >= rn) return;
+  evict_stub_record(R, rec[i], depth[i]);
 }
 
 // ---- partial handles (forest.h EL_STUB).  All of these run only on a handle that holds stubs, or
@@ -566,6 +600,133 @@ static void forest_evict(kh_trie* h, const uint32_t* tries, uint64_t k, uint64_t
   *n_evicted = ntries;
 }
 
+// subtrees back to stubs (kh_trie_evict_subtrees): every refusal is decided on the host before
+// anything changes; the probe reads, and only the delete and the stub rewrite write
+static void evict_subtrees(kh_trie* h, const uint32_t* tries, const uint8_t* paths32, const uint8_t* depths,
+                           uint64_t n, uint8_t* status, uint8_t* hashes32, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!h->sps.empty()) throw KhError{KH_EINVAL, "kh_trie_evict_subtrees: a savepoint is open"};
+  if (n >= (1ULL << 31)) throw KhError{KH_EINVAL, "prefix list too large"};
+  for (uint64_t i = 0; i < n; ++i)
+    if (depths[i] == 0 || depths[i] > 64)
+      throw KhError{KH_EINVAL, "kh_trie_evict_subtrees: a depth of 0 (a root is never a stub) or above 64"};
+  // the list sorted by (trie, zero-padded path, depth): a prefix that equals or extends another
+  // shows between neighbours
+  std::vector<uint64_t> pw(n * 4);
+  std::vector<uint32_t> order(n);
+  for (uint64_t i = 0; i < n; ++i) {
+    uint64_t w[4];
+    words_of(paths32 + 32 * i, 32, w);
+    for (int q = 0; q < 4; ++q) pw[4 * i + q] = prefix_word(w, depths[i], q);
+    order[i] = (uint32_t)i;
+  }
+  auto trie_of = [&](uint32_t i) { return h->forest ? tries[i] : 0u; };
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    if (trie_of(a) != trie_of(b)) return trie_of(a) < trie_of(b);
+    const int c = key_cmp(&pw[4ull * a], &pw[4ull * b]);
+    if (c) return c < 0;
+    return depths[a] != depths[b] ? depths[a] < depths[b] : a < b;
+  });
+  for (uint64_t s = 0; s + 1 < n; ++s) {
+    const uint32_t a = order[s], b = order[s + 1];
+    if (trie_of(a) == trie_of(b) && prefix_eq(&pw[4ull * a], &pw[4ull * b], std::min(depths[a], depths[b])))
+      throw KhError{KH_EINVAL, "kh_trie_evict_subtrees: a listed prefix equals or extends another"};
+  }
+  trie_settle(h);
+  if (n == 0) return;
+  memset(status, EVICT_NONE, n);
+  memset(hashes32, 0, n * 32);
+  const uint64_t rn = h->rn;
+  if (rn == 0 || h->mcap == 0) return;
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  // the probe, in sorted order; the DONE prefixes keep that order as the flag pass's list
+  std::vector<uint32_t> ht(n);
+  std::vector<uint64_t> hp(n * 4);
+  std::vector<uint8_t> hd(n);
+  for (uint64_t s = 0; s < n; ++s) {
+    ht[s] = trie_of(order[s]);
+    hd[s] = depths[order[s]];
+    memcpy(&hp[4 * s], &pw[4ull * order[s]], 32);
+  }
+  Layout L;
+  uint32_t *dt, *drec, *flag, *pos, *list;
+  uint64_t *dp, *dhash;
+  uint8_t *dd, *dstat, *dkey;
+  unsigned long long* tot;
+  char* scr;
+  L.add_all(n, dt, drec);
+  L.add_all(n * 4, dp, dhash);
+  L.add_all(n, dd, dstat, dkey);
+  L.add_all(rn, flag, pos, list);
+  L.add(scr, scan_scratch_size(rn + 1, 4));
+  L.add(tot, 8);
+  place(h->gbuf, L);
+  const Recs R = recs_of(h);
+  HIPCHK(hipMemcpyAsync(dt, ht.data(), n * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dp, hp.data(), n * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dd, hd.data(), n, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_evsub_probe, GRID(n, BS), dim3(BS), 0, st, map_of(h), R, EvictList{dt, dp, dd, n}, dstat, dhash,
+                     drec, dkey);
+  LAUNCH_CHECK();
+  std::vector<uint8_t> sstat(n), skey(n);
+  std::vector<uint32_t> srec(n);
+  std::vector<uint64_t> shash(n * 4);
+  HIPCHK(hipMemcpyAsync(sstat.data(), dstat, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(skey.data(), dkey, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(srec.data(), drec, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(shash.data(), dhash, n * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  uint64_t m = 0, akeys = 0;
+  for (uint64_t s = 0; s < n; ++s) {
+    status[order[s]] = sstat[s];
+    memcpy(hashes32 + 32ull * order[s], &shash[4 * s], 32);
+    if (sstat[s] != EVICT_DONE) continue;
+    ht[m] = ht[s];  // (m <= s: compacted in place, the order kept)
+    hd[m] = hd[s];
+    srec[m] = srec[s];
+    memmove(&hp[4 * m], &hp[4 * s], 32);
+    akeys += skey[s];
+    ++m;
+  }
+  if (m == 0) return;
+  ++h->epoch;  // (an export cursor ends)
+  HIPCHK(hipMemcpyAsync(dt, ht.data(), m * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dp, hp.data(), m * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dd, hd.data(), m, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(drec, srec.data(), m * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(tot, 0, 64, st));
+  hipLaunchKernelGGL(k_evsub_flags, GRID(rn, BS), dim3(BS), 0, st, R, rn, EvictList{dt, dp, dd, m}, flag, tot + 1);
+  LAUNCH_CHECK();
+  scan_u32(flag, pos, rn, (uint32_t*)tot, scr, st);
+  HIPCHK(hipMemcpyAsync(c->h_pinned, tot, 64, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // (the host vectors are read by now)
+  const uint64_t nl = (uint32_t)c->h_pinned[0], nkeys = c->h_pinned[1] + akeys, nstub = c->h_pinned[2];
+  try {
+    if (nl) {
+      hipLaunchKernelGGL(k_evict_list, GRID(rn, BS), dim3(BS), 0, st, rn, (const uint32_t*)flag, (const uint32_t*)pos,
+                         nl, list);
+      LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_map_delete, GRID(nl, BS), dim3(BS), 0, st, map_of(h), R, (const uint32_t*)list, nl,
+                         (const uint32_t*)nullptr, (uint64_t)0, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p,
+                         (uint64_t*)nullptr);
+      LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_evsub_stub, GRID(m, BS), dim3(BS), 0, st, R, (const uint32_t*)drec, (const uint8_t*)dd, m, rn);
+    LAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(st));
+  } catch (...) {
+    h->broken = true;  // the map may hold part of the eviction: only a free from here
+    throw;
+  }
+  h->rdead += nl;
+  h->nleaves -= nkeys;
+  h->nstubs = h->nstubs + m - nstub;
+  out[0] = m;
+  out[1] = nkeys;
+  out[2] = nl;
+}
+
 // a host node store into the context's staging buffers (in_vals, in_voff), checked first:
 // KH_EINVAL before anything is staged
 static int stage_store(kh_ctx* c, const uint8_t* enc, const uint64_t* off, uint64_t n) {
@@ -700,6 +861,26 @@ int kh_forest_evict(kh_trie* f, const uint32_t* tries, uint64_t k, uint64_t* n_e
     HIPCHK(hipSetDevice(f->c->dev));
     forest_evict(f, tries, k, &dropped);
     if (n_evicted) *n_evicted = dropped;
+  })
+}
+
+int kh_trie_evict_subtrees(kh_trie* h, const uint32_t* tries, const uint8_t* paths32, const uint8_t* depths,
+                           uint64_t n, uint8_t* status, uint8_t* hashes32, uint64_t* n_evicted, uint64_t* n_keys,
+                           uint64_t* n_records) {
+  if (n_evicted) *n_evicted = 0;
+  if (n_keys) *n_keys = 0;
+  if (n_records) *n_records = 0;
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  if (n && (!paths32 || !depths || !status || !hashes32 || (h->forest && !tries)))
+    return set_err(KH_EINVAL, "null buffer");
+  API_TRY({
+    HANDLE_LOCK(h);
+    HIPCHK(hipSetDevice(h->c->dev));
+    uint64_t out[3];
+    evict_subtrees(h, tries, paths32, depths, n, status, hashes32, out);
+    if (n_evicted) *n_evicted = out[0];
+    if (n_keys) *n_keys = out[1];
+    if (n_records) *n_records = out[2];
   })
 }
 

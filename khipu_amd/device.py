@@ -262,6 +262,27 @@ class _Versioned:
         check(lib().kh_trie_fill_nodes(self.h, _ptr(ed), _ptr(eo), len(encs), ctypes.byref(n), None))
         return int(n.value)
 
+    def _evict_subtrees(self, prefixes, trie_ids):
+        from .codec import nibbles_to_path32
+        prefixes = [list(p) for p in prefixes]
+        n = len(prefixes)
+        if any(len(p) > 255 for p in prefixes):
+            raise ValueError("a prefix is at most 64 nibbles")
+        # (a depth above 64 is passed on with its first 64 nibbles: the library refuses it)
+        pb = np.frombuffer(b"".join(nibbles_to_path32(p[:64]) for p in prefixes) + b"\0", np.uint8).copy()
+        db = np.asarray([len(p) for p in prefixes] + [0], np.uint8)
+        tb = np.asarray(list(trie_ids) + [0], np.uint32) if trie_ids is not None else None
+        status = np.zeros(max(n, 1), np.uint8)
+        hs = np.zeros(32 * max(n, 1), np.uint8)
+        ne, nk, nr = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._sync()
+        check(lib().kh_trie_evict_subtrees(self.h, tb.ctypes.data if tb is not None else None, pb.ctypes.data,
+                                           db.ctypes.data, n, status.ctypes.data, hs.ctypes.data, ctypes.byref(ne),
+                                           ctypes.byref(nk), ctypes.byref(nr)))
+        res = [(int(status[i]), hs[32 * i:32 * i + 32].tobytes()
+                if status[i] in (_lib.KH_EVICT_DONE, _lib.KH_EVICT_STUB) else None) for i in range(n)]
+        return res, {"evicted": int(ne.value), "keys": int(nk.value), "records": int(nr.value)}
+
     def _need(self, keys, trie_ids):
         keys = list(keys)
         n = len(keys)
@@ -385,6 +406,13 @@ class ResidentTrie(_Versioned):
         """[hash or None] per key: the node to fetch before a commit of that key can walk past the
         stub its path reaches (kh_trie_need_host); None where the path is resident."""
         return self._need(keys, None)
+
+    def evict_subtrees(self, prefixes):
+        """Turn held subtrees back into stubs (kh_trie_evict_subtrees).  prefixes: nibble sequences,
+        each naming the subtree that hangs there.  Returns ([(status, hash or None)], counters):
+        status one of KH_EVICT_NONE / DONE / STUB / EMBEDDED, the hash the one to fetch to bring the
+        subtree back (DONE, STUB); counters {evicted, keys, records}."""
+        return self._evict_subtrees(prefixes, None)
 
     def _flag(self, hash_keys):
         """The trie's key encoder is fixed at open (as the reference's implicit
@@ -1085,6 +1113,12 @@ class ResidentForest(_Versioned):
         """queries: [(trie_id, key)] -> [hash or None], as ResidentTrie.need."""
         q = list(queries)
         return self._need([k for _, k in q], [t for t, _ in q])
+
+    def evict_subtrees(self, prefixes, tries=True):
+        """prefixes: [(trie_id, nibbles)] -> ([(status, hash or None)], counters), as
+        ResidentTrie.evict_subtrees.  (tries=None passes no trie array: the library refuses it.)"""
+        q = list(prefixes)
+        return self._evict_subtrees([p for _, p in q], [t for t, _ in q] if tries is not None else None)
 
     def load_nodes(self, roots, nodes, partial=False):
         """Page tries in (kh_forest_load_nodes): roots {trie_id: root}, nodes {hash: encoding} or a
