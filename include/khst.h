@@ -449,7 +449,8 @@ int kh_forest_load_nodes_host(kh_trie* f, const uint32_t* tries, const uint8_t* 
  * stub, and so does kh_trie_prove, whose proof for such a key is the resident nodes of the path
  * (kh_verify_proofs calls it KH_PROOF_SHORT); kh_trie_need_host returns per key the hash of the
  * stub its walk reaches (need_flag 1, need32[32i..)) or need_flag 0 -- what to fetch before a
- * commit of those keys, the collapse case apart.  kh_trie_export_nodes skips stubs (a branch
+ * commit of those keys, the collapse case apart (kh_trie_commit_witness_host lists a batch's whole
+ * need, the collapse case included).  kh_trie_export_nodes skips stubs (a branch
  * encodes a stub child by the reference the stub keeps): the export of a partial handle is the
  * witness it holds.  kh_trie_nodes_by_hash never answers from a stub.  To kh_forest_roots,
  * kh_forest_evict, kh_trie_compact, kh_trie_copy, savepoints and rollbacks a stub is a live record
@@ -477,6 +478,55 @@ int kh_trie_stubs(const kh_trie* h, uint64_t* n);
 int kh_trie_missing(const kh_trie* h, uint32_t* tries, uint8_t* hashes32, uint64_t cap, uint64_t* n);
 int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
                       uint8_t* need_flag, uint8_t* need32);
+
+/* The commit witness of a batch: every node a handle opened by kh_trie_open_partial (or
+ * kh_forest_load_partial) at the current root(s) must hold to accept the batch at the first attempt
+ * -- what a full node hands a stateless verifier or a replica that works from witnesses.  All
+ * arrays are host arrays.  Keys, klen, trie ids and the batch contract are those of
+ * kh_trie_apply_host / kh_forest_apply_host: upserts first, then deletes; the last op on a key
+ * wins, so a key in both lists is a delete; a repeated key counts once; trie ids are read on a
+ * forest and ignored on a single trie (they may be NULL there).  No values are taken: the witness
+ * does not depend on them.  flags: 0, or KH_HASH_KEYS on a handle opened with it.
+ *
+ * The witness W is a node table in the layout and order of kh_trie_prove with KH_PROVE_SHARED
+ * (hashes32, rlp, off; each (record, node) once, ascending records, the upper node before the
+ * branch under its extension; a node two tries of a forest hold appears once per trie).  It holds
+ *   (1) the shared proof table of every op key, upserts and deletes alike -- deletes of absent
+ *       keys and upserts that end at an empty slot or inside an extension included;
+ *   (2) for every branch on those paths that the batch leaves with exactly one non-empty slot,
+ *       that slot having held a subtree before the batch: the node hanging in it (the upper node
+ *       of its record: a leaf, a branch, or an extension without its branch) when the parent
+ *       refers to it by hash -- the child the reference's fix loads (MerklePatriciaTrie.scala:
+ *       430-477).  An embedded child is part of the parent's bytes and adds nothing.  A slot is
+ *       non-empty after the batch when a key of the post-batch key set lies under it, so a branch
+ *       that loses all its keys empties its parent's slot and the parent may be the one that
+ *       collapses; a root branch left one child is covered by the same rule.
+ * *n_collapse (nullable) = the table nodes in (2) and not in (1).
+ * W is sufficient (the partial handle opened from it commits the batch to the root the full handle
+ * gives) and minimal (without any one node the open, or the commit, is refused with KH_ENODE).
+ *
+ * Read-only on the handle: root, records, last roots, write-back set, the kh_trie_missing list and
+ * export cursors are as before; with a savepoint open it reads the commits since the savepoint.
+ * Work and memory follow the ops and their paths, never the handle's size.
+ *
+ * KH_OK with *n_nodes = 0: no ops, empty tries only, or ids the forest does not hold.
+ * KH_ENOSPC when node_cap or rlp_cap is short: only *n_nodes and *rlp_len are written, and a retry
+ * with exactly those sizes succeeds.
+ * KH_ENODE on a handle with stubs: the list the commit of the batch on this handle would leave in
+ * kh_trie_missing -- if any op's walk reaches a stub, the distinct (trie id, hash to fetch) pairs
+ * of those stubs; otherwise the stubs of unknown kind that (2) would move.  *n_missing is their
+ * number, at most miss_cap pairs are written (any order), nothing else is.  A surviving stub that
+ * stands for the branch under a present extension is not missing (its extension is the collapse
+ * child; an extension cut down to nothing leaves no collapse child).
+ * KH_EINVAL: a null handle or required output, a klen or KH_HASH_KEYS the handle's commits refuse,
+ * trie ids NULL on a forest, nup + ndel >= 2^31, unknown flags.  Whether the commit would be
+ * refused for another reason (the key of a value-only branch removed) is not judged: that key's
+ * path is listed. */
+int kh_trie_commit_witness_host(kh_trie* h, const uint32_t* up_trie, const uint8_t* up_keys, uint64_t nup,
+                                const uint32_t* del_trie, const uint8_t* del_keys, uint64_t ndel, uint32_t klen,
+                                uint32_t flags, uint8_t* hashes32, uint64_t node_cap, uint8_t* rlp, uint64_t rlp_cap,
+                                uint64_t* off, uint64_t* n_nodes, uint64_t* rlp_len, uint64_t* n_collapse,
+                                uint32_t* miss_tries, uint8_t* miss_hashes32, uint64_t miss_cap, uint64_t* n_missing);
 
 /* Every trie the forest holds (>= 1 key), ascending ids, with its root: one streaming pass over
  * the records, read-only on the handle.  KH_ENOSPC with *n_tries when cap is short. */

@@ -1001,6 +1001,73 @@ JNIEXPORT jbyteArray JNICALL Java_khipu_trie_gpu_Khst_need(JNIEnv* env, jclass c
   return out;
 }
 
+/* The commit witness of a batch (kh_trie_commit_witness_host): every node a handle opened by
+ * openPartial / forestLoadPartial at the current root(s) needs to apply the upserts (upKeys) and
+ * deletes (delKeys; klen bytes a key, upTrie / delTrie a forest's trie ids or null) at the first
+ * attempt, into the caller's arrays as prove fills them (hashes / rlp / off).  sizes[0..3] = nodes /
+ * RLP bytes / collapse children / missing nodes.  Returns the node count, or -1 when an array is
+ * too small (sizes hold what the call needs: grow and call again).  A partial handle that lacks
+ * nodes of the witness throws MPTNodeMissingException with the first hash, after writing the
+ * entries that fit into missing (nullable; 36 bytes an entry, as missing() packs them). */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_commitWitness(JNIEnv* env, jclass cls, jlong handle, jintArray upTrie,
+                                                              jbyteArray upKeys, jintArray delTrie, jbyteArray delKeys,
+                                                              jint klen, jbyteArray hashes, jbyteArray rlp,
+                                                              jlongArray off, jbyteArray missing, jlongArray sizes) {
+  (void)cls;
+  if (klen <= 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "commitWitness: klen must be positive");
+    return 0;
+  }
+  const uint64_t nup = (uint64_t)len_of(env, upKeys) / (uint64_t)klen;
+  const uint64_t ndel = (uint64_t)len_of(env, delKeys) / (uint64_t)klen;
+  if ((upTrie && (uint64_t)len_of(env, upTrie) < nup) || (delTrie && (uint64_t)len_of(env, delTrie) < ndel) ||
+      len_of(env, off) < 1) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "commitWitness: trie ids / off shorter than the keys need");
+    return 0;
+  }
+  uint64_t node_cap = (uint64_t)len_of(env, hashes) / 32;
+  if ((uint64_t)len_of(env, off) - 1 < node_cap) node_cap = (uint64_t)len_of(env, off) - 1;
+  const uint64_t rlp_cap = (uint64_t)len_of(env, rlp), miss_cap = (uint64_t)len_of(env, missing) / 36;
+  Bufs b = {0};
+  const uint32_t* ut = in_i(env, &b, upTrie);
+  const uint8_t* uk = in_b(env, &b, upKeys);
+  const uint32_t* dt = in_i(env, &b, delTrie);
+  const uint8_t* dk = in_b(env, &b, delKeys);
+  uint8_t* hs = out_buf(env, &b, hashes, 1);
+  uint8_t* rl = out_buf(env, &b, rlp, 1);
+  uint64_t* of = out_buf(env, &b, off, 8);
+  uint32_t* mt = bufs_alloc(&b, 4 * (size_t)(miss_cap ? miss_cap : 1));
+  uint8_t* mh = bufs_alloc(&b, 32 * (size_t)(miss_cap ? miss_cap : 1));
+  uint8_t* packed = bufs_alloc(&b, 36 * (size_t)(miss_cap ? miss_cap : 1));
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t nn = 0, nb = 0, nc = 0, nm = 0;
+  const int rc = kh_trie_commit_witness_host(H(handle), ut, uk, nup, dt, dk, ndel, (uint32_t)klen, 0, hs, node_cap, rl,
+                                             rlp_cap, of, &nn, &nb, &nc, mt, mh, miss_cap, &nm);
+  uint8_t first[32] = {0};
+  if (rc == KH_OK) {
+    put_b(env, hashes, hs, 32 * nn);
+    put_b(env, rlp, rl, nb);
+    put_l(env, off, of, nn + 1);
+  } else if (rc == KH_ENODE) {
+    const uint64_t w = nm < miss_cap ? nm : miss_cap;
+    for (uint64_t i = 0; i < w; ++i) {
+      for (int q = 0; q < 4; ++q) packed[36 * i + q] = (uint8_t)(mt[i] >> (8 * q));
+      memcpy(packed + 36 * i + 4, mh + 32 * i, 32);
+    }
+    put_b(env, missing, packed, 36 * w);
+    if (w) memcpy(first, mh, 32);
+  }
+  bufs_free(&b);
+  const jlong sz[4] = {(jlong)nn, (jlong)nb, (jlong)nc, (jlong)nm};
+  put_l(env, sizes, sz, 4);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh_hash(env, rc, first);
+    return 0;
+  }
+  return (jlong)nn;
+}
+
 /* every trie the forest holds, ascending ids: 36 bytes a trie, the id (4 bytes, little endian)
  * then its root.  The count is negotiated: KH_ENOSPC reports it, another thread's commit or load
  * can change it again, so the loop grows and retries (bounded), as get does. */

@@ -68,7 +68,7 @@ EXPORTS = (
     "kh_forest_load_partial_host", "kh_trie_fill_nodes", "kh_trie_fill_nodes_host", "kh_trie_stubs",
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
     "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
-    "kh_trie_diffs_host", "kh_dev_trie_diffs", "kh_trie_evict_subtrees",
+    "kh_trie_diffs_host", "kh_dev_trie_diffs", "kh_trie_evict_subtrees", "kh_trie_commit_witness_host",
 )
 
 
@@ -213,6 +213,9 @@ def lib():
     L.kh_trie_stubs.argtypes = [vp, ctypes.POINTER(u64)]
     L.kh_trie_missing.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.kh_trie_need_host.argtypes = [vp, vp, vp, u32, u64, vp, vp]
+    L.kh_trie_commit_witness_host.argtypes = [vp, vp, vp, u64, vp, vp, u64, u32, u32, vp, u64, vp, u64, vp,
+                                              ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp,
+                                              u64, ctypes.POINTER(u64)]
     L.kh_trie_range_host.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      ctypes.POINTER(i32), vp, vp]
     L.kh_dev_trie_range.argtypes = L.kh_trie_range_host.argtypes

@@ -296,6 +296,51 @@ class _Versioned:
                                       flag.ctypes.data, hs.ctypes.data))
         return [hs[32 * i:32 * i + 32].tobytes() if flag[i] else None for i in range(n)]
 
+    def commit_witness_raw(self, up_keys, up_ids, del_keys, del_ids, caps=(0, 0), miss_cap=0, flags=0):
+        """One kh_trie_commit_witness_host call with the capacities caps = (nodes, encoding bytes):
+        (rc, (n_nodes, rlp_len, n_collapse, n_missing), (hashes, rlp, off, miss_tries, miss_hashes))."""
+        up_keys, del_keys = list(up_keys), list(del_keys)
+        klen = len(up_keys[0]) if up_keys else (len(del_keys[0]) if del_keys else 32)
+        ub = np.frombuffer(b"".join(up_keys) + b"\0", np.uint8).copy()
+        db = np.frombuffer(b"".join(del_keys) + b"\0", np.uint8).copy()
+        ut = np.asarray(list(up_ids) + [0], np.uint32) if up_ids is not None else None
+        dt = np.asarray(list(del_ids) + [0], np.uint32) if del_ids is not None else None
+        cn, cb = caps
+        hs = np.zeros(32 * max(cn, 1), np.uint8)
+        rl = np.zeros(max(cb, 1), np.uint8)
+        of = np.zeros(cn + 1, np.uint64)
+        mt = np.zeros(max(miss_cap, 1), np.uint32)
+        mh = np.zeros(32 * max(miss_cap, 1), np.uint8)
+        nn, nl, nc, nm = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.ctx._sync()
+        rc = lib().kh_trie_commit_witness_host(
+            self.h, ut.ctypes.data if ut is not None else None, ub.ctypes.data, len(up_keys),
+            dt.ctypes.data if dt is not None else None, db.ctypes.data, len(del_keys), klen, flags, hs.ctypes.data, cn,
+            rl.ctypes.data, cb, of.ctypes.data, ctypes.byref(nn), ctypes.byref(nl), ctypes.byref(nc), mt.ctypes.data,
+            mh.ctypes.data, miss_cap, ctypes.byref(nm))
+        return rc, (int(nn.value), int(nl.value), int(nc.value), int(nm.value)), (hs, rl, of, mt, mh)
+
+    def _commit_witness(self, up_keys, up_ids, del_keys, del_ids):
+        up_keys, del_keys = list(up_keys), list(del_keys)
+        caps, miss_cap = (0, 0), 0
+        for _ in range(4):
+            rc, (nn, nl, nc, nm), (hs, rl, of, mt, mh) = self.commit_witness_raw(up_keys, up_ids, del_keys, del_ids,
+                                                                                caps, miss_cap)
+            if rc == _lib.KH_ENOSPC:
+                caps = (nn, nl)
+                continue
+            if rc == _lib.KH_ENODE:
+                if nm > miss_cap:
+                    miss_cap = nm
+                    continue
+                e = _lib.MPTNodeMissingException(rc, lib().kh_last_error().decode())
+                e.missing = [(int(mt[i]), mh[32 * i:32 * i + 32].tobytes()) for i in range(nm)]
+                raise e
+            check(rc)
+            self.witness_nodes = nn  # (a forest lists a node two tries hold once per trie)
+            return {hs[32 * j:32 * j + 32].tobytes(): rl[int(of[j]):int(of[j + 1])].tobytes() for j in range(nn)}, nc
+        raise RuntimeError("kh_trie_commit_witness_host: size negotiation failed")
+
     def nodes_by_hash(self, hashes):
         """getMptNodeByHash over the current version (kh_trie_nodes_by_hash): [encoding or None]
         per 32-byte hash, at most 4096 a call."""
@@ -433,6 +478,15 @@ class ResidentTrie(_Versioned):
         uv, uo = _pack_dev([v for _, v in ups], self.dev)
         dk, _ = _pack_dev(dels, self.dev)
         return self.commit_dev(uk, uv, uo, len(ups), dk, len(dels), klen, hash_keys, stats)
+
+    def commit_witness(self, upserts=(), deletes=()):
+        """({hash: encoding}, n_collapse): every node a handle opened by from_witness at the current
+        root needs to commit(upserts, deletes) at the first attempt -- the paths of the op keys and the
+        siblings a collapsing branch is merged with (kh_trie_commit_witness_host).  Takes the batch
+        commit takes; the values are ignored and the trie is left unchanged.  On a partial handle
+        that lacks some of it: MPTNodeMissingException, .missing the [(0, hash)] to fetch."""
+        ups = list(upserts.items()) if isinstance(upserts, dict) else list(upserts)
+        return self._commit_witness([k for k, _ in ups], None, list(deletes), None)
 
     def commit_dev(self, up_keys, up_vals, up_voff, nup, del_keys, ndel, klen=32, hash_keys=None, stats=None):
         root = np.zeros(32, np.uint8)
@@ -1076,6 +1130,14 @@ class ResidentForest(_Versioned):
                                     len(dels), klen, tries.ctypes.data, roots.ctypes.data, cap, ctypes.byref(nt),
                                     ctypes.byref(st)))
         return {int(tries[i]): roots[32 * i:32 * i + 32].tobytes() for i in range(nt.value)}
+
+    def commit_witness(self, upserts=(), deletes=()):
+        """As ResidentTrie.commit_witness for commit's [(trie_id, key, value)] upserts and
+        [(trie_id, key)] deletes: ({hash: encoding}, n_collapse), what load_partial needs at the
+        current roots; .missing of the exception is [(trie_id, hash)]."""
+        ups, dels = list(upserts), list(deletes)
+        return self._commit_witness([k for _, k, _ in ups], [t for t, _, _ in ups], [k for _, k in dels],
+                                    [t for t, _ in dels])
 
     @classmethod
     def from_nodes(cls, ctx, roots, nodes, hash_keys=False, emit=False):
