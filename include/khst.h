@@ -966,6 +966,72 @@ int kh_dev_verify_ranges(kh_ctx* ctx, const uint8_t* d_roots32, const uint8_t* d
                          const uint64_t* d_ent_off, const uint8_t* d_enc, const uint64_t* d_off, uint64_t n_nodes,
                          uint8_t* status, uint8_t* more, uint8_t* missing32);
 
+/* Range responses INTO a partial handle: the receiving half of a range sync.  Where
+ * kh_verify_ranges judges a response on its own and keeps nothing, this call replaces the stubs of
+ * a partial handle (kh_trie_open_partial, kh_forest_load_partial) that lie inside the delivered
+ * span with the subtrees built from the entries, and keeps the result only if no root moves: a
+ * stub remembers the hash its parent holds, so the trie itself checks the rebuild.  A root-only
+ * handle becomes the full resident trie page by page, usable for gets, proofs, ranges, diffs and
+ * commits on the synced part the whole time; a forest takes a GetStorageRanges answer (many whole
+ * small tries and one tail) in one call.
+ * Inputs: the entry layout of kh_verify_ranges (range s is entries ent_off[s] .. ent_off[s+1]).
+ * Keys are 32-byte TRIE keys and are never hashed: on a KH_HASH_KEYS handle they are the kec256
+ * values a range scan returns.  tries[s] names range s's trie (ignored and nullable on a single
+ * trie, which takes one range a call); origins32 NULL: all zero.  No node set is taken: the caller
+ * first gives the response's boundary-proof nodes to kh_trie_fill_nodes (content-addressed against
+ * the stubs, so harmless even if the range is then refused).
+ * Per range s, trie t, origin o, entries k_1 .. k_m, hi = k_m:
+ *   1. keys strictly ascending, k_1 >= o, every value >= 1 byte, else BAD_ORDER (decided before the
+ *      handle is read).
+ *   2. t not resident (no node at its root; forests only): the entries claim to be the WHOLE trie,
+ *      which is built from empty and must hash to roots32[32s..) (required then), else BAD_ROOT;
+ *      with m = 0 OK requires EMPTY_TRIE_HASH and loads nothing.
+ *   3. t resident: roots32[32s..) must be its current root, else BAD_ROOT (roots32 NULL: no claim).
+ *      A live stub whose missing node starts at nibble depth md below key prefix p spans
+ *      [p|0..0, p|f..f]; it is INSIDE when that span lies within [o, hi] ([o, ff..ff] when m = 0).
+ *      An entry whose walk reaches an inside stub drops the stub: the entries under its prefix
+ *      are built in its place.  An entry that reaches any other stub needs a node the handle
+ *      lacks: MISSING, and kh_trie_missing lists the (trie, hash) pairs exactly as a refused commit
+ *      does.  An inside stub no entry reaches: BAD_ROOT (INCOMPLETE when m = 0).  An entry that
+ *      lands on a resident leaf must carry that leaf's value.  The trie's root after the rebuild
+ *      must equal its root before; everything else is BAD_ROOT: an omitted key, an invented key,
+ *      a changed value, and a value-only branch inside the span (the limit of kh_verify_ranges).
+ *   4. All or nothing per call: if any status is not OK the handle is exactly as before (root,
+ *      records, export bytes and order, kh_trie_size, kh_trie_stubs, last roots, write-back set)
+ *      and the call returns KH_OK with the statuses written: they say which ranges to drop before
+ *      a retry.  The ranges are judged in stages -- order, root claims and INCOMPLETE first, then
+ *      MISSING, then the rebuilt roots -- and a call refused at one stage leaves the ranges only a
+ *      later stage would refuse at OK; a retry without the refused ranges reaches that stage.
+ *   5. On success every listed trie keeps its root; kh_trie_size grows by *n_keys, kh_trie_stubs
+ *      falls by *n_stubs; stubs_left[s] = live stubs of trie t afterwards (0: the trie is whole).
+ *      On a KH_EMIT_NODES handle kh_trie_emit_nodes gives exactly the hash-referenced nodes the
+ *      handle did not hold before and holds now (what a sync client writes to its store; a trie
+ *      loaded whole includes its root node).  kh_forest_last_roots lists the call's tries with
+ *      their unchanged roots.  Export cursors end.
+ *   6. OK vouches for the HANDLE: afterwards it holds every key of the trie in [o, hi].  A response
+ *      that omits a key the handle already held is not detected; kh_verify_ranges is the call that
+ *      judges a response on its own.
+ * KH_EINVAL, nothing changed: a null handle or required array; tries NULL on a forest; a trie id
+ * listed twice; nr or the entry total >= 2^31; a savepoint open (as for kh_trie_fill_nodes); a
+ * trie that is not resident named on a single-trie handle, or on a forest without roots32.
+ * nr = 0 is KH_OK.  KH_ENODE is never the return code.
+ * status, stubs_left (nullable), n_keys and n_stubs (nullable) are host arrays / scalars.
+ * kh_dev_trie_fill_ranges: every input array in HBM on the handle's stream, with the alignment
+ * rules and preconditions of kh_dev_verify_ranges (8-byte aligned roots, origins, keys and
+ * offsets; d_ent_off[0] = 0; monotone offsets). */
+int kh_trie_fill_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* roots32,
+                             const uint8_t* origins32, uint64_t nr,
+                             const uint8_t* keys32, const uint8_t* vals, const uint64_t* voff,
+                             const uint64_t* ent_off,
+                             uint8_t* status, uint64_t* stubs_left,
+                             uint64_t* n_keys, uint64_t* n_stubs);
+int kh_dev_trie_fill_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_roots32,
+                            const uint8_t* d_origins32, uint64_t nr,
+                            const uint8_t* d_keys32, const uint8_t* d_vals, const uint64_t* d_voff,
+                            const uint64_t* d_ent_off,
+                            uint8_t* status, uint64_t* stubs_left,
+                            uint64_t* n_keys, uint64_t* n_stubs);
+
 /* HBM held by a resident trie or forest.  Records and the value heap are append-only between
  * compactions: a commit appends the records and values it makes and leaves the ones it
  * replaces dead (~18 MB per configs[2] block).  records / heap_bytes: in use; live_records /

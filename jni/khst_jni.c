@@ -1786,6 +1786,66 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_verifyRanges(JNIEnv* env, jclas
   return bad;
 }
 
+/* Range responses into a partial handle (kh_trie_fill_ranges_host): the stubs inside each delivered
+ * span are replaced by the subtrees built from the entries, all or nothing, kept only if no root
+ * moves.  nr = entOff.length - 1 ranges: tries (an int a range; null on a single trie), roots (32
+ * bytes a range, or null: no claim), origins (32 bytes a range, or null: all zero), the entries'
+ * 32-byte TRIE keys (never hashed) with their values packed in vals / voff, range s holding entries
+ * entOff[s] .. entOff[s + 1].  The boundary-proof nodes go to fillNodes first.  Out: status
+ * (KH_RANGE_*, a byte a range), stubsLeft (a long a range, or null), gained (or null): {keys
+ * gained, stubs replaced}.  Returns the number of ranges whose status is not KH_RANGE_OK: anything
+ * but 0 and the handle is as it was (a KH_RANGE_MISSING range's hashes: missing). */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_fillRanges(JNIEnv* env, jclass cls, jlong handle, jintArray tries,
+                                                           jbyteArray roots, jbyteArray origins, jbyteArray keys,
+                                                           jbyteArray vals, jlongArray voff, jlongArray entOff,
+                                                           jbyteArray status, jlongArray stubsLeft, jlongArray gained) {
+  (void)cls;
+  if (len_of(env, entOff) < 1 || len_of(env, voff) < 1) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "fillRanges: entOff and voff must hold at least one offset");
+    return 0;
+  }
+  const uint64_t nr = count_of(env, entOff), ne = count_of(env, voff);
+  if ((tries && (uint64_t)len_of(env, tries) < nr) || (roots && (uint64_t)len_of(env, roots) < 32 * nr) ||
+      (origins && (uint64_t)len_of(env, origins) < 32 * nr) || (uint64_t)len_of(env, status) < nr ||
+      (stubsLeft && (uint64_t)len_of(env, stubsLeft) < nr) || (gained && len_of(env, gained) < 2) ||
+      (uint64_t)len_of(env, keys) < 32 * ne) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "fillRanges: an array is too short for its ranges / entries");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint32_t* ts = in_i(env, &b, tries);
+  const uint8_t* rt = in_b(env, &b, roots);
+  const uint8_t* og = in_b(env, &b, origins);
+  const uint8_t* ks = in_b(env, &b, keys);
+  const uint8_t* vs = in_b(env, &b, vals);
+  const uint64_t* vo = in_l(env, &b, voff);
+  const uint64_t* eo = in_l(env, &b, entOff);
+  uint8_t* st = out_buf(env, &b, status, 1);
+  uint64_t* sl = out_buf(env, &b, stubsLeft, 8);
+  if (bufs_failed(env, &b)) return 0;
+  /* the library reads keys / voff up to entOff[nr] and vals up to voff[ne] */
+  if (eo[nr] > ne || vo[ne] > (uint64_t)len_of(env, vals)) {
+    bufs_free(&b);
+    throw_cls(env, "java/lang/IllegalArgumentException", "fillRanges: entOff / voff point past keys / vals");
+    return 0;
+  }
+  uint64_t g[2] = {0, 0};
+  const int rc = kh_trie_fill_ranges_host(H(handle), ts, rt, og, nr, ks, vs, vo, eo, st, sl, &g[0], &g[1]);
+  jlong bad = 0;
+  if (rc == KH_OK) {
+    for (uint64_t s = 0; s < nr; ++s) bad += st[s] != KH_RANGE_OK;
+    put_b(env, status, st, nr);
+    if (stubsLeft) put_l(env, stubsLeft, sl, nr);
+    if (gained) put_l(env, gained, g, 2);
+  }
+  bufs_free(&b);
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return bad;
+}
+
 /* ---- versions (Ledger.scala:237-271 retry / reject; TrieAccounts.rootHash; copy) ---- */
 JNIEXPORT jint JNICALL Java_khipu_trie_gpu_Khst_savepoint(JNIEnv* env, jclass cls, jlong handle) {
   (void)cls;

@@ -69,6 +69,7 @@ EXPORTS = (
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
     "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
     "kh_trie_diffs_host", "kh_dev_trie_diffs", "kh_trie_evict_subtrees", "kh_trie_commit_witness_host",
+    "kh_trie_fill_ranges_host", "kh_dev_trie_fill_ranges",
 )
 
 
@@ -224,6 +225,9 @@ def lib():
     L.kh_dev_trie_ranges.argtypes = L.kh_trie_ranges_host.argtypes
     L.kh_verify_ranges.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]
     L.kh_dev_verify_ranges.argtypes = [vp] + L.kh_verify_ranges.argtypes
+    L.kh_trie_fill_ranges_host.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u64),
+                                           ctypes.POINTER(u64)]
+    L.kh_dev_trie_fill_ranges.argtypes = L.kh_trie_fill_ranges_host.argtypes
     L.kh_trie_diff_host.argtypes = [vp, u32, vp, u32, vp, vp, u64, u64, vp, vp, vp, vp, ctypes.POINTER(u64),
                                     ctypes.POINTER(u64), ctypes.POINTER(i32), vp, vp]
     L.kh_dev_trie_diff.argtypes = L.kh_trie_diff_host.argtypes

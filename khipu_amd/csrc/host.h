@@ -24,6 +24,7 @@
 #include "../../include/khst.h"
 #include "trie_ops.h"
 #include "forest.h"
+#include "fillrange.h"
 #include "layout.h"
 
 struct HostStage;  // khst.hip: host inputs still streaming in (BuildArgs::hs)
@@ -519,6 +520,15 @@ void make_private(kh_trie* h);
 void query_check(const kh_trie* h, const uint32_t* trie, uint32_t klen, uint64_t n, bool hash);
 void stage_query_keys(kh_ctx* c, const uint32_t* trie, const uint8_t* keys, uint32_t klen, uint64_t n,
                       uint8_t*& dk, uint32_t*& dt);
+// kh_trie_fill_ranges (fillrange.h): n entries (device arrays; trie ids for a forest) as the upserts
+// of one commit in fill mode, under a savepoint of its own.  accept() runs after the commit, the
+// new roots in h->d_tries / h->d_roots, and says keep or roll back.  Returns FILL_KEPT, or with the
+// handle as it was: FILL_MISSING (an entry reached a stub that is not inside: FillMode::miss, the
+// hashes in the handle's missing list), FILL_MOVED (a stub of unknown kind would have been
+// re-anchored: the tries in the missing list), FILL_REFUSED (accept said no).
+enum FillResult { FILL_KEPT = 0, FILL_MISSING = 1, FILL_MOVED = 2, FILL_REFUSED = 3 };
+FillResult commit_fill(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, const uint8_t* d_vals,
+                       const uint64_t* d_voff, uint64_t n, const FillMode& fm, const std::function<bool()>& accept);
 
 }  // namespace khst
 
@@ -529,6 +539,13 @@ __global__ void k_map_delete(AMap M, Recs R, const uint32_t* list, uint64_t n, c
                              uint32_t* touched, uint8_t* replaced, uint64_t* mlog);
 __global__ void k_map_insert(AMap M, Recs R, uint64_t base, uint64_t nb, const uint32_t* list, uint64_t n,
                              unsigned long long* err, unsigned long long* used, uint64_t* mlog);
+// load_kernels.hip's, which a commit in fill mode (kh_trie_fill_ranges) runs in place of k_f_descend
+// and k_stub_missing, and after k_f_elem_flags on the write-back selection:
+__global__ void k_fill_descend(FOps O, AMap M, Recs R, FillMode F, uint32_t* touched, uint8_t* replaced,
+                               uint32_t* tlist, unsigned long long* ctr, uint8_t* vbf);
+__global__ void k_fill_missing(Recs R, FillMode F, const uint32_t* list, uint64_t n, uint64_t cap, uint32_t* out_trie,
+                               uint64_t* out_hash, unsigned long long* cnt);
+__global__ void k_fill_sel(Topo T, Elems E, const uint32_t* tries, AMap M, Recs R, uint64_t B, uint8_t* sel);
 // export_kernels.hip's, which kh_trie_prove runs in list mode over its hits:
 __global__ void k_export_sizes(AMap M, Recs R, const uint8_t* heap, const uint64_t* list, uint64_t r0, uint64_t n,
                                uint32_t filter, uint32_t* stash, uint32_t* cnt, uint32_t* bytes);

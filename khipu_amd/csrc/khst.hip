@@ -3686,6 +3686,12 @@ struct FCommit {  // one commit's inputs (device buffers)
   // into the account bodies here, so the account phase need not wait for the rest
   std::function<void(hipStream_t, uint32_t)> after_roots;  // (the stream, the commit's trie count)
   hipEvent_t inputs_ready = nullptr;  // the inputs were staged on another stream (HostPack): wait first
+  // fill mode (kh_trie_fill_ranges, fillrange.h; commit_fill below): the keys are trie keys (never
+  // hashed), the descent drops the stubs inside each trie's span, and a re-put of a leaf under a
+  // depth-63 branch replaces it (a range response re-delivers keys; it is no khipu put).  A
+  // refusal leaves its kind in *fill_refused (FILL_MISSING / FILL_MOVED).
+  const FillMode* fill = nullptr;
+  int* fill_refused = nullptr;
 };
 
 static int emit_nodes_dev(kh_ctx* c, DevBuf& out, uint64_t* n_nodes, uint64_t* rlp_len);
@@ -3784,14 +3790,17 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   // makes runs past the tie kernel, and the whole sort falls back to 256 bits.  Such a fallback
   // turns the 24-bit form off for the handle's next 16 commits.  Unhashed keys (structured, their
   // leading bytes often equal) never take it.
-  if ((h->flags & KH_HASH_KEYS) && S.sb <= 18 && nops <= (segd ? (1ull << 17) : (1ull << 19)) && h->lo24_off == 0)
+  // (nor a fill: a page's keys are neighbours in key order and share their leading bits)
+  if ((h->flags & KH_HASH_KEYS) && !F.fill && S.sb <= 18 && nops <= (segd ? (1ull << 17) : (1ull << 19)) &&
+      h->lo24_off == 0)
     S.rs_lo = 40;
   if (h->lo24_off) --h->lo24_off;
   const bool defer = (bool)F.before_values;
   S.chk = defer ? nullptr : F.chk;
   if (segd && ((F.nup && !F.up_trie) || (F.ndel && !F.del_trie))) throw KhError{KH_EINVAL, "forest ops need trie ids"};
   // the op keys (unless hashed above) and trie ids, upserts then deletes: one launch
-  bool copy_keys = !(h->flags & KH_HASH_KEYS);
+  const bool hk = (h->flags & KH_HASH_KEYS) && !F.fill;  // (a fill's keys are the trie's own)
+  bool copy_keys = !hk;
   if (copy_keys && (((uintptr_t)F.up_keys | (uintptr_t)F.del_keys) & 7)) {  // unaligned caller keys: copies
     if (F.nup) HIPCHK(hipMemcpyAsync(K, F.up_keys, F.nup * 32, hipMemcpyDeviceToDevice, st));
     if (F.ndel) HIPCHK(hipMemcpyAsync(K + 4 * F.nup, F.del_keys, F.ndel * 32, hipMemcpyDeviceToDevice, st));
@@ -3803,7 +3812,6 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
                      segd ? F.del_trie : nullptr, K, Tid, S.ctr);
   // the keys hashed (the trie's key encoder) and the composite sort keys made, one launch
   {
-    const bool hk = h->flags & KH_HASH_KEYS;
     const uint32_t* sg = segd ? Tid : nullptr;
     unsigned long long* fl = S.ctr + CTR_TIE;
     uint32_t* hdr = (uint32_t*)S.rs_scratch;
@@ -3909,8 +3917,12 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   recs_reserve(h, h->rn + 16);
   if (h->mcap == 0) map_rebuild(h, nops + 1024);
   h->flags_dirty = true;  // until the touched records die (k_map_delete) or are untouched
-  hipLaunchKernelGGL(k_f_descend, GRID(nd, BS), dim3(BS), 0, st, O, map_of(h), recs_of(h), (uint32_t*)h->touched.p,
-                     (uint8_t*)h->replaced.p, tlist, fctr, vbf);
+  if (F.fill)
+    hipLaunchKernelGGL(k_fill_descend, GRID(nd, BS), dim3(BS), 0, st, O, map_of(h), recs_of(h), *F.fill,
+                       (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p, tlist, fctr, vbf);
+  else
+    hipLaunchKernelGGL(k_f_descend, GRID(nd, BS), dim3(BS), 0, st, O, map_of(h), recs_of(h), (uint32_t*)h->touched.p,
+                       (uint8_t*)h->replaced.p, tlist, fctr, vbf);
   LAUNCH_CHECK();
   // ---- 3. elements: the gather (grid-stride over the device's touched count), one sync
   auto gather = [&](bool redo) {
@@ -3941,10 +3953,15 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       Lm.add(mc, 8);
       place(h->selb, Lm);
       HIPCHK(hipMemsetAsync(mc, 0, 8, st));
-      hipLaunchKernelGGL(k_stub_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)tlist, ntl, ntl,
-                         mt, mh, mc);
+      if (F.fill)  // (the inside stubs the descent dropped are in the list too: not missing)
+        hipLaunchKernelGGL(k_fill_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), *F.fill, (const uint32_t*)tlist,
+                           ntl, ntl, mt, mh, mc);
+      else
+        hipLaunchKernelGGL(k_stub_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)tlist, ntl,
+                           ntl, mt, mh, mc);
       LAUNCH_CHECK();
       stub_missing_read(h, mt, mh, mc, ntl);
+      if (F.fill_refused) *F.fill_refused = FILL_MISSING;
     }
     if (ntl) {
       hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
@@ -4057,6 +4074,7 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
         }
         h->flags_dirty = false;
         h->heap_n = hb;  // (the upserts' values past it are dropped)
+        if (F.fill_refused) *F.fill_refused = FILL_MOVED;
         throw KhError{KH_ENODE, MSG_STUB};
       }
     }
@@ -4137,6 +4155,10 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
                        esrc, rein);
     LAUNCH_CHECK();
     scan_exclusive<uint32_t>(isnew, nrank, m, tot, sscr, st);
+    if (F.fill && keep_em) {  // a re-delivered leaf and a stub's own extension were held before
+      hipLaunchKernelGGL(k_fill_sel, GRID(m + B, BS), dim3(BS), 0, st, T, E, (const uint32_t*)tries, M, R, B, sel);
+      LAUNCH_CHECK();
+    }
     journal_begin(ntl + m, B + m);
     // old anchors out of the map (touched records, element sources), then touched records die
     hipLaunchKernelGGL(k_map_delete, GRID(ntl + m, BS), dim3(BS), 0, st, M, R, (const uint32_t*)tlist, ntl,
@@ -4375,6 +4397,36 @@ struct Txn {
     }
   }
 };
+// kh_trie_fill_ranges' commit (host.h): the entries as upserts in fill mode, all or nothing
+FillResult khst::commit_fill(kh_trie* h, const uint32_t* d_trie, const uint8_t* d_keys, const uint8_t* d_vals,
+                             const uint64_t* d_voff, uint64_t n, const FillMode& fm,
+                             const std::function<bool()>& accept) {
+  int refused = 0;
+  FCommit F;
+  F.up_trie = d_trie;
+  F.up_keys = d_keys;
+  F.up_vals = d_vals;
+  F.up_voff = d_voff;
+  F.nup = n;
+  F.klen = 32;
+  F.fill = &fm;
+  F.fill_refused = &refused;
+  Txn txn(h, nullptr);
+  try {
+    forest_commit(h, F, nullptr);
+  } catch (const KhError& e) {
+    if (e.code != KH_ENODE || !refused) throw;
+    txn.rollback();  // (nothing was written: the savepoint goes)
+    return (FillResult)refused;
+  }
+  if (!accept()) {
+    txn.rollback();
+    return FILL_REFUSED;
+  }
+  txn.release();
+  return FILL_KEPT;
+}
+
 // MerklePatriciaTrie.copy (MerklePatriciaTrie.scala:556): an independent handle holding the
 // current version (records, anchor map, value heap, last roots and write-back set) in HBM
 static kh_trie* trie_copy(kh_trie* h) {

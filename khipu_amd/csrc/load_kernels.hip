@@ -1,4 +1,5 @@
-// The forest load, kh_forest_roots, kh_forest_evict and the partial handles' open, fill and need:
+// The forest load, kh_forest_roots, kh_forest_evict, the partial handles' open, fill and need, and
+// the range fills (kh_trie_fill_ranges: fillrange.h; a service of the partial handles, and this unit is theirs):
 // their kernels (load.h holds the bodies), then the host drivers and the C entry points (host.h).
 // A compilation unit of its own: a code object of its own cannot shift the placement of the hot
 // kernels of khst.hip (tests/test_code_layout.py).  The kernels take the POD views and raw
@@ -8,6 +9,8 @@
 #include <cstdint>
 
 #include "load.h"
+#include "rangeverify.h"
+#include "keccak.h"
 #include "host.h"
 #include "wave.h"
 
@@ -227,6 +230,228 @@ __global__ void __launch_bounds__(BS) k_need(AMap M, Recs R, const uint64_t* K, 
   const bool stub = r != NONE && R.rdb[r] == EL_STUB;
   flag[o] = stub ? 1 : 0;
   for (int q = 0; q < 4; ++q) hash[4 * o + q] = stub ? R.rbref[4ull * r + q] : 0;
+}
+
+// ---- kh_trie_fill_ranges (fillrange.h): range responses into a partial handle.  Cold like the rest
+// of this unit: one thread per range, entry, record, op or element.
+__global__ void k_rv_order(RvIn I, uint64_t ne, uint32_t* bad);  // rangeverify_kernels.hip's order check
+
+// the call as the kernels see it: arrays by range s (input order), or by sorted position j = pos[s]
+// (the listed tries in ascending id order, as FillMode wants them)
+struct FillPlan {
+  const uint32_t* tries;    // [nr] nullable: trie 0
+  const uint64_t* roots;    // [nr*4] nullable: no claim
+  const uint64_t* origins;  // [nr*4] nullable: all zero
+  const uint64_t* keys;     // [ne*4]
+  const uint64_t* ent_off;  // [nr+1]
+  uint64_t nr;
+  const uint32_t* pos;      // [nr]
+  uint64_t *lo, *hi;        // [nr*4] by j: the span
+  uint32_t* resident;       // [nr] by s
+  uint64_t* oldroot;        // [nr*4] by s: a resident trie's root
+  uint32_t *live, *inside, *dropped, *miss;  // [nr] by j
+  uint8_t* status;          // [nr] by s
+};
+KH_HD bool words_eq4(const uint64_t* a, const uint64_t* b) {
+  return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3];
+}
+// Per range: residency (a live record at anchor (t, 0)) and the root that record stands for, the
+// span, and what is decided before the commit: the order, the root claim, an empty trie's root.
+__global__ void __launch_bounds__(BS) k_fill_plan(FillPlan P, AMap M, Recs R, bool has_map, const uint32_t* bad) {
+  const uint64_t s = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (s >= P.nr) return;
+  const uint32_t t = P.tries ? P.tries[s] : 0u, j = P.pos[s];
+  const uint64_t e0 = P.ent_off[s], e1 = P.ent_off[s + 1];
+  const uint64_t zero[4] = {0, 0, 0, 0};
+  const uint32_t r = has_map ? map_find(M, R, t, 0, zero) : NONE;
+  uint64_t root[4] = {0, 0, 0, 0};
+  if (r != NONE) {
+    const uint32_t rl = R.rrl[r];
+    if (rl >= 32) {
+      for (int q = 0; q < 4; ++q) root[q] = R.rref[4ull * r + q];
+    } else {  // a root node shorter than a hash is referenced by its encoding; the root is its hash
+      kec256_msg<false>((const uint8_t*)&R.rref[4ull * r], rl, root);
+    }
+  }
+  for (int q = 0; q < 4; ++q) {
+    P.lo[4 * j + q] = P.origins ? P.origins[4 * s + q] : 0;
+    P.hi[4 * j + q] = e1 > e0 ? P.keys[4 * (e1 - 1) + q] : ~0ULL;
+    P.oldroot[4 * s + q] = root[q];
+  }
+  P.resident[s] = r != NONE ? 1u : 0u;
+  uint8_t st = RANGE_OK;
+  if (bad[s]) {
+    st = RANGE_BAD_ORDER;
+  } else if (r == NONE) {
+    if (e1 == e0 && P.roots && !bytes_eq32((const uint8_t*)(P.roots + 4 * s), empty_root_hash())) st = RANGE_BAD_ROOT;
+  } else if (P.roots && !words_eq4(P.roots + 4 * s, root)) {
+    st = RANGE_BAD_ROOT;
+  }
+  P.status[s] = st;
+}
+// a forest's op trie ids: entry i names its range's trie
+__global__ void __launch_bounds__(BS) k_fill_optrie(const uint32_t* tries, const uint64_t* ent_off, uint64_t nr,
+                                                    uint64_t ne, uint32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i >= ne) return;
+  out[i] = tries[rv_range_of(ent_off, nr, i)];
+}
+// The streaming pass: one thread a record, reading its first 64-byte line (key prefix, trie, db,
+// rmask, live).  Stubs are few among the records and a wave's stubs mostly of one trie: the lanes
+// of one trie are counted by ballot and their first lane adds once per counter.
+__global__ void __launch_bounds__(BS) k_fill_stubs(Recs R, uint64_t n, FillMode F, uint32_t* live, uint32_t* inside) {
+  const uint64_t r = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  uint32_t j = NONE;
+  bool in = false;
+  if (r < n && load_is_stub(R, r)) {
+    const uint32_t t = R.rt[r];
+    j = seg_of(F.tries, F.nt, t);
+    if (j >= F.nt || F.tries[j] != t) {
+      j = NONE;
+    } else {
+      in = fill_inside(R.key(r), R.rmask[r] & 0xFF, F.lo + 4 * j, F.hi + 4 * j);
+    }
+  }
+  for (uint64_t pend = __ballot(j != NONE); pend;) {  // (wave-uniform: every lane stays for the ballots)
+    const int leader = __ffsll((long long)pend) - 1;
+    const uint32_t lj = (uint32_t)__shfl((int)j, leader);
+    const uint64_t grp = __ballot(j == lj), gin = __ballot(j == lj && in);
+    if ((int)__lane_id() == leader) {
+      atomicAdd(&live[lj], (uint32_t)__popcll(grp));
+      if (gin) atomicAdd(&inside[lj], (uint32_t)__popcll(gin));
+    }
+    pend &= ~grp;
+  }
+}
+// a range without entries is complete only if no stub of its trie lies at or after its origin
+__global__ void __launch_bounds__(BS) k_fill_pre(FillPlan P) {
+  const uint64_t s = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (s >= P.nr || P.status[s] != RANGE_OK) return;
+  if (P.ent_off[s + 1] == P.ent_off[s] && P.resident[s] && P.inside[P.pos[s]]) P.status[s] = RANGE_INCOMPLETE;
+}
+// After the commit: a range with entries keeps RANGE_OK only if its trie's new root is the old one
+// (the given one for a trie loaded whole) and the descent dropped every inside stub of the pass.
+__global__ void __launch_bounds__(BS) k_fill_judge(FillPlan P, const uint32_t* ctries, const uint64_t* croots,
+                                                   uint32_t nct) {
+  const uint64_t s = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (s >= P.nr || P.status[s] != RANGE_OK || P.ent_off[s + 1] == P.ent_off[s]) return;
+  const uint32_t t = P.tries ? P.tries[s] : 0u, j = P.pos[s];
+  const uint32_t g = seg_of(ctries, nct, t);
+  const uint64_t* want = P.resident[s] ? P.oldroot + 4 * s : P.roots + 4 * s;
+  const bool ok = g < nct && ctries[g] == t && words_eq4(croots + 4 * g, want) && P.inside[j] == P.dropped[j];
+  if (!ok) P.status[s] = RANGE_BAD_ROOT;
+}
+
+// The descent of a commit in fill mode: khst.hip's k_f_descend, but a stub the walk reaches is
+// tested against its trie's span.  Inside: marked touched (the gather brings nothing for it, the
+// delete takes it out of the map) and counted once, by the lane whose exchange marked it.  Not
+// inside: a missing node as in a commit (ctr[3] bit 1), its trie flagged.  A leaf under a depth-63
+// branch is replaced like any leaf: a response re-delivers keys, it makes no value-only branch.
+__global__ void __launch_bounds__(BS) k_fill_descend(FOps O, AMap M, Recs R, FillMode F, uint32_t* touched,
+                                                     uint8_t* replaced, uint32_t* tlist, unsigned long long* ctr,
+                                                     uint8_t* vbf) {
+  const uint64_t o = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  auto mark = [&](bool want, uint32_t r) {  // (k_f_descend's: the first lane of a run of one record exchanges)
+    const uint32_t rr = want ? r : NONE;
+    const uint32_t prev = __shfl_up(rr, 1);
+    const bool lead = want && ((threadIdx.x & 63) == 0 || prev != rr);
+    bool first = false;
+    if (lead && __hip_atomic_load(&touched[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+      first = atomicExch(&touched[r], 1u) == 0u;
+    const uint64_t slot = wave_claim(&ctr[0], first);
+    if (first) tlist[slot] = r;
+    return first;
+  };
+  const bool live = o < O.n;
+  const uint64_t* K = O.key + 4 * (live ? o : 0);
+  const uint32_t t = live ? O.trie[o] : 0;
+  uint32_t d = 0;
+  bool active = live, repl = false, lost = live, vb = false;
+  for (int step = 0; step < 70 && __ballot(active); ++step) {
+    uint32_t r = NONE, drop_j = NONE;
+    if (active) {
+      r = map_find(M, R, t, d, K);
+      if (r == NONE) {
+        active = lost = false;
+      } else {
+        const uint32_t db = R.rdb[r];
+        if (db == EL_LEAF) {
+          if (words_eq4(R.key(r), K)) {
+            replaced[r] = 1;  // keys are unique in the batch: one op per leaf
+            repl = true;
+          }
+          active = lost = false;
+        } else if (db == VB_DEPTH) {  // a value-only branch: only its own key reaches it, and stays one
+          if (words_eq4(R.key(r), K))
+            vb = repl = true;
+          else
+            r = NONE;
+          active = lost = false;
+        } else if (const int lcp = lcp_nibbles(load_key(K, 0), load_key(R.key(r), 0)); lcp < (int)db) {
+          // leaves the extension (the subtree is gathered whole), or a stub
+          const uint32_t md = R.rmask[r] & 0xFF;
+          if (db == EL_STUB && !(md > d && lcp < (int)md)) {
+            const uint32_t j = seg_of(F.tries, F.nt, t);  // (every op's trie is listed)
+            if (j < F.nt && fill_inside(R.key(r), md, F.lo + 4 * j, F.hi + 4 * j)) {
+              drop_j = j;
+            } else {
+              atomicOr(&ctr[3], 2ULL);
+              if (j < F.nt) F.miss[j] = 1;  // (every writer stores the same 1)
+            }
+          } else {
+            r = NONE;
+          }
+          active = lost = false;
+        } else {
+          d = db + 1;
+        }
+      }
+    }
+    const bool first = mark(r != NONE, r);
+    if (first && drop_j != NONE) atomicAdd(&F.dropped[drop_j], 1u);
+  }
+  wave_atomic_add(&ctr[1], repl ? 1ULL : 0ULL);
+  wave_atomic_add(&ctr[6], vb ? 1ULL : 0ULL);
+  if (live) vbf[o] = vb ? 1 : 0;
+  if (lost) ctr[2] = 3;
+}
+// the refused fill's missing list: k_stub_missing without the inside stubs (dropped, not missing)
+__global__ void __launch_bounds__(BS) k_fill_missing(Recs R, FillMode F, const uint32_t* list, uint64_t n, uint64_t cap,
+                                                     uint32_t* out_trie, uint64_t* out_hash,
+                                                     unsigned long long* cnt) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = list[i];
+  if (!load_is_stub(R, r)) return;
+  const uint32_t j = seg_of(F.tries, F.nt, R.rt[r]);
+  if (j < F.nt && fill_inside(R.key(r), R.rmask[r] & 0xFF, F.lo + 4 * j, F.hi + 4 * j)) return;
+  const unsigned long long t = atomicAdd(cnt, 1ULL);
+  if (t >= cap) return;
+  out_trie[t] = R.rt[r];
+  for (int q = 0; q < 4; ++q) out_hash[4 * t + q] = R.rbref[4ull * r + q];
+}
+// The write-back selection of a fill (after k_f_elem_flags, before the old anchors leave the map):
+// the set is the nodes the handle did not hold.  A commit selects every upsert's leaf; one that
+// replaces the resident leaf of its key (a re-delivered boundary key) was held.  It selects the
+// extension of a branch built where a stub stood; a STUB_BRANCH stub's own extension was held.
+__global__ void __launch_bounds__(BS) k_fill_sel(Topo T, Elems E, const uint32_t* tries, AMap M, Recs R, uint64_t B,
+                                                 uint8_t* sel) {
+  const uint64_t g = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (g < T.m) {
+    if (E.src[T.sidx[g]] != NONE) return;
+    const uint32_t t = tries[T.sseg ? T.sseg[g] : 0], a = (uint32_t)(T.lf_pd[g] + 1);
+    const uint32_t old = map_find(M, R, t, a, T.skey + 4 * g);
+    if (old != NONE && R.rdb[old] == EL_LEAF && words_eq4(R.key(old), T.skey + 4 * g)) sel[g] = 0;
+    return;
+  }
+  const uint64_t j = g - T.m;
+  if (j >= B || !T.br_ext[j]) return;
+  const uint64_t f = T.br_first[j];
+  const uint32_t t = tries[T.sseg ? T.sseg[f] : 0], db = T.br_depth[j], d = db - T.br_ext[j];
+  const uint32_t old = map_find(M, R, t, d, T.skey + 4 * f);
+  if (old == NONE || R.rdb[old] != EL_STUB || (R.rmask[old] & 0xFFu) != db) return;
+  const uint32_t xrl = T.ex_rlen[j] >= 32 ? 32 : T.ex_rlen[j];
+  if (R.rrl[old] == xrl && words_eq4(&R.rref[4ull * old], T.ex_ref + 4 * j)) sel[T.m + 2 * j + 1] = 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -964,6 +1189,244 @@ int kh_trie_need_host(kh_trie* h, const uint32_t* trie, const uint8_t* keys, uin
     HIPCHK(hipMemcpyAsync(need_flag, df, n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(need32, dh, n * 32, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+  })
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// host: range fills (fillrange.h)
+// ---------------------------------------------------------------------------
+// nr ranges of ne entries in all into handle h, every input in HBM on its stream; ht: the trie ids
+// on the host (a single trie: empty).  The ranges are judged in stages -- order, root claims and
+// completeness before the commit; missing nodes at its descent; roots and dropped stubs after it --
+// and a call refused at one stage reports the ranges later stages would judge as they stand.
+// Host syncs: one before the commit (statuses, residency), the commit's own, one after it.
+// what refuses the call whatever the ranges hold (checked before anything is staged)
+static void fill_precheck(const kh_trie* h, std::vector<uint32_t> ht, uint64_t nr) {
+  if (!h->sps.empty()) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: a savepoint is open"};
+  if (!h->forest && nr > 1)
+    throw KhError{KH_EINVAL, "kh_trie_fill_ranges: a trie id listed twice (a single trie takes one range a call)"};
+  std::sort(ht.begin(), ht.end());
+  if (std::adjacent_find(ht.begin(), ht.end()) != ht.end())
+    throw KhError{KH_EINVAL, "kh_trie_fill_ranges: a trie id listed twice"};
+}
+static void fill_ranges_dev(kh_trie* h, const uint32_t* d_tries, const std::vector<uint32_t>& ht, const uint8_t* d_roots,
+                            const uint8_t* d_orig, uint64_t nr, const uint8_t* d_keys, const uint8_t* d_vals,
+                            const uint64_t* d_voff, const uint64_t* d_eo, uint64_t ne, uint8_t* status,
+                            uint64_t* stubs_left, uint64_t* n_keys, uint64_t* n_stubs) {
+  fill_precheck(h, ht, nr);
+  trie_settle(h);
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  const bool forest = h->forest;
+  // the listed tries in ascending order: sorted position j of range s, no id twice
+  std::vector<uint32_t> order(nr), pos(nr), strie(nr, 0);
+  for (uint64_t s = 0; s < nr; ++s) order[s] = (uint32_t)s;
+  if (forest) {
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ht[a] < ht[b]; });
+    for (uint64_t j = 0; j < nr; ++j) strie[j] = ht[order[j]];
+  }
+  for (uint64_t j = 0; j < nr; ++j) pos[order[j]] = (uint32_t)j;
+  Layout L;
+  uint32_t *dstrie, *dpos, *bad, *resident, *live, *inside, *dropped, *miss, *optrie;
+  uint64_t *lo, *hi, *oldroot;
+  uint8_t* dst;
+  L.add_all(nr, dstrie, dpos);
+  L.add_all(nr, bad, resident, live, inside, dropped, miss);  // (back to back: one memset)
+  L.add_all(nr * 4, lo, hi, oldroot);
+  L.add(optrie, ne + 1, forest);
+  L.add(dst, nr);
+  place(h->gbuf, L);
+  HIPCHK(hipMemcpyAsync(dstrie, strie.data(), nr * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dpos, pos.data(), nr * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(bad, 0, (size_t)((char*)(miss + nr) - (char*)bad), st));
+  const RvIn I{(const uint64_t*)d_roots, (const uint64_t*)d_orig, nullptr, nr, (const uint64_t*)d_keys, d_voff, d_eo,
+               NStore{}};
+  const FillPlan P{forest ? d_tries : nullptr, (const uint64_t*)d_roots, (const uint64_t*)d_orig,
+                   (const uint64_t*)d_keys, d_eo, nr, dpos, lo, hi, resident, oldroot, live, inside, dropped, miss, dst};
+  const FillMode FM{dstrie, lo, hi, (uint32_t)nr, dropped, miss};
+  const bool has_map = h->rn && h->mcap;
+  if (ne) {
+    hipLaunchKernelGGL(k_rv_order, GRID(ne, BS), dim3(BS), 0, st, I, ne, bad);
+    LAUNCH_CHECK();
+    if (forest) {
+      hipLaunchKernelGGL(k_fill_optrie, GRID(ne, BS), dim3(BS), 0, st, d_tries, d_eo, nr, ne, optrie);
+      LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL(k_fill_plan, GRID(nr, BS), dim3(BS), 0, st, P, has_map ? map_of(h) : AMap{}, recs_of(h), has_map,
+                     (const uint32_t*)bad);
+  LAUNCH_CHECK();
+  if (has_map && h->nstubs) {
+    hipLaunchKernelGGL(k_fill_stubs, GRID(h->rn, BS), dim3(BS), 0, st, recs_of(h), h->rn, FM, live, inside);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_fill_pre, GRID(nr, BS), dim3(BS), 0, st, P);
+  LAUNCH_CHECK();
+  // (the outputs are staged: an error writes nothing)
+  std::vector<uint8_t> hst(nr), hroots(nr * 32), hclaim(d_roots ? nr * 32 : 0);
+  std::vector<uint32_t> hres(nr), hlive(nr), hdrop(nr, 0), hmiss(nr);
+  HIPCHK(hipMemcpyAsync(hst.data(), dst, nr, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hres.data(), resident, nr * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hlive.data(), live, nr * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hroots.data(), oldroot, nr * 32, hipMemcpyDeviceToHost, st));
+  if (d_roots) HIPCHK(hipMemcpyAsync(hclaim.data(), d_roots, nr * 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (uint64_t s = 0; s < nr; ++s) {
+    if (hres[s]) continue;
+    if (!forest) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: the trie is not resident (open it partial first)"};
+    if (!d_roots) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: a trie that is not resident needs its root"};
+  }
+  auto all_ok = [&] { return std::all_of(hst.begin(), hst.end(), [](uint8_t x) { return x == RANGE_OK; }); };
+  auto finish = [&](uint64_t keys, uint64_t stubs) {
+    memcpy(status, hst.data(), nr);
+    for (uint64_t s = 0; s < nr && stubs_left; ++s) stubs_left[s] = hlive[pos[s]] - hdrop[pos[s]];
+    if (n_keys) *n_keys = keys;
+    if (n_stubs) *n_stubs = stubs;
+  };
+  if (!all_ok()) return finish(0, 0);
+  const uint64_t leaves0 = h->nleaves;
+  if (ne) {
+    const FillResult fr =
+        commit_fill(h, forest ? optrie : nullptr, d_keys, d_vals, d_voff, ne, FM, [&] {
+          hipLaunchKernelGGL(k_fill_judge, GRID(nr, BS), dim3(BS), 0, st, P, (const uint32_t*)h->d_tries,
+                             (const uint64_t*)h->d_roots, (uint32_t)h->tries.size());
+          LAUNCH_CHECK();
+          HIPCHK(hipMemcpyAsync(hst.data(), dst, nr, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(hdrop.data(), dropped, nr * 4, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipStreamSynchronize(st));
+          return all_ok();
+        });
+    if (fr == FILL_MISSING) {  // kh_trie_missing lists the hashes, as after a refused commit
+      HIPCHK(hipMemcpyAsync(hmiss.data(), miss, nr * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (uint64_t s = 0; s < nr; ++s)
+        if (hmiss[pos[s]]) hst[s] = RANGE_MISSING;
+    } else if (fr == FILL_MOVED) {  // a stub of unknown kind re-anchored: the entries do not rebuild that trie
+      for (uint64_t s = 0; s < nr; ++s)
+        if (std::find(h->miss_tries.begin(), h->miss_tries.end(), forest ? ht[s] : 0u) != h->miss_tries.end())
+          hst[s] = RANGE_BAD_ROOT;
+      h->miss_tries.clear();
+      h->miss_hashes.clear();
+    }
+    if (fr != FILL_KEPT) {
+      std::fill(hdrop.begin(), hdrop.end(), 0u);
+      if (all_ok()) throw KhError{KH_EINTERNAL, "kh_trie_fill_ranges: a refused fill names no range"};
+      return finish(0, 0);
+    }
+  } else {  // nothing to ingest; cursors end and the write-back set is the (empty) call's
+    ++h->epoch;
+    h->em_n = h->em_bytes = 0;
+    h->em_valid = (h->flags & KH_EMIT_NODES) != 0;
+  }
+  uint64_t ndrop = 0;
+  for (uint64_t j = 0; j < nr; ++j) ndrop += hdrop[j];
+  h->nstubs -= ndrop;
+  // the last roots: the call's tries, ascending, each with the root it kept
+  h->tries.assign(strie.begin(), strie.end());
+  h->roots.resize(nr * 32);
+  for (uint64_t j = 0; j < nr; ++j) {
+    const uint64_t s = order[j];
+    memcpy(h->roots.data() + 32 * j, (hres[s] ? hroots.data() : hclaim.data()) + 32 * s, 32);
+  }
+  h->d_tries = nullptr;
+  h->d_roots = nullptr;
+  finish(h->nleaves - leaves0, ndrop);
+}
+
+extern "C" {
+
+int kh_dev_trie_fill_ranges(kh_trie* h, const uint32_t* d_tries, const uint8_t* d_roots32, const uint8_t* d_origins32,
+                            uint64_t nr, const uint8_t* d_keys32, const uint8_t* d_vals, const uint64_t* d_voff,
+                            const uint64_t* d_ent_off, uint8_t* status, uint64_t* stubs_left, uint64_t* n_keys,
+                            uint64_t* n_stubs) {
+  if (n_keys) *n_keys = 0;
+  if (n_stubs) *n_stubs = 0;
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  if (nr >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_trie_fill_ranges: batch too large");
+  if (!d_ent_off || !d_voff || (nr && (!status || (h->forest && !d_tries))))
+    return set_err(KH_EINVAL, "kh_trie_fill_ranges: null array");
+  // (roots, origins and keys are read as 64-bit words, the offsets are 64-bit words)
+  if ((((uintptr_t)d_roots32 | (uintptr_t)d_origins32 | (uintptr_t)d_keys32 | (uintptr_t)d_voff | (uintptr_t)d_ent_off) &
+       7) != 0 || ((uintptr_t)d_tries & 3) != 0)
+    return set_err(KH_EINVAL, "kh_dev_trie_fill_ranges: roots, origins, keys and offsets must be 8-byte aligned");
+  API_TRY({
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    if (nr == 0) return KH_OK;
+    uint64_t eo[2];
+    std::vector<uint32_t> ht(h->forest ? nr : 0);
+    HIPCHK(hipMemcpyAsync(&eo[0], d_ent_off, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&eo[1], d_ent_off + nr, 8, hipMemcpyDeviceToHost, c->st));
+    if (h->forest) HIPCHK(hipMemcpyAsync(ht.data(), d_tries, nr * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (eo[0] != 0) return set_err(KH_EINVAL, "kh_dev_trie_fill_ranges: ent_off[0] must be 0");
+    const uint64_t ne = eo[1];
+    if (ne >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_trie_fill_ranges: batch too large");
+    if (ne && !d_keys32) return set_err(KH_EINVAL, "kh_trie_fill_ranges: null array");
+    fill_ranges_dev(h, d_tries, ht, d_roots32, d_origins32, nr, d_keys32, d_vals, d_voff, d_ent_off, ne, status,
+                    stubs_left, n_keys, n_stubs);
+  })
+}
+
+int kh_trie_fill_ranges_host(kh_trie* h, const uint32_t* tries, const uint8_t* roots32, const uint8_t* origins32,
+                             uint64_t nr, const uint8_t* keys32, const uint8_t* vals, const uint64_t* voff,
+                             const uint64_t* ent_off, uint8_t* status, uint64_t* stubs_left, uint64_t* n_keys,
+                             uint64_t* n_stubs) {
+  if (n_keys) *n_keys = 0;
+  if (n_stubs) *n_stubs = 0;
+  if (!h) return set_err(KH_EINVAL, "null handle");
+  if (nr >= (1ULL << 31)) return set_err(KH_EINVAL, "kh_trie_fill_ranges: batch too large");
+  if (!ent_off || !voff || (nr && (!status || (h->forest && !tries))))
+    return set_err(KH_EINVAL, "kh_trie_fill_ranges: null array");
+  API_TRY({
+    for (uint64_t s = 0; s < nr; ++s)
+      if (ent_off[s + 1] < ent_off[s]) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: ent_off must not decrease"};
+    const uint64_t e0 = ent_off[0], ne = ent_off[nr] - e0;
+    if (ne >= (1ULL << 31)) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: batch too large"};
+    if (ne && !keys32) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: null array"};
+    for (uint64_t i = e0; i < e0 + ne; ++i) {
+      if (voff[i + 1] < voff[i]) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: voff must not decrease"};
+      if (voff[i + 1] - voff[i] > 0xFFFFFFFFull)
+        throw KhError{KH_EINVAL, "kh_trie_fill_ranges: a value longer than 2^32 - 1 bytes"};
+    }
+    const uint64_t v0 = voff[e0], vb = voff[e0 + ne] - v0;
+    if (vb && !vals) throw KhError{KH_EINVAL, "kh_trie_fill_ranges: null array"};
+    if (nr == 0) return KH_OK;
+    HANDLE_LOCK(h);
+    kh_ctx* c = h->c;
+    HIPCHK(hipSetDevice(c->dev));
+    hipStream_t st = c->st;
+    // offsets rebased to zero; everything staged into one buffer
+    std::vector<uint64_t> reo(nr + 1), rvo(ne + 1);
+    for (uint64_t s = 0; s <= nr; ++s) reo[s] = ent_off[s] - e0;
+    for (uint64_t i = 0; i <= ne; ++i) rvo[i] = voff[e0 + i] - v0;
+    std::vector<uint32_t> ht;
+    if (h->forest) ht.assign(tries, tries + nr);
+    fill_precheck(h, ht, nr);
+    Layout Li;
+    uint8_t *droots, *dorig, *dkeys, *dvals;
+    uint64_t *dvoff, *deo;
+    uint32_t* dtries;
+    Li.add(droots, nr * 32, roots32 != nullptr);
+    Li.add(dorig, nr * 32, origins32 != nullptr);
+    Li.add(dkeys, ne * 32 + 32);
+    Li.add(dvals, vb + 64);
+    Li.add(dvoff, ne + 1);
+    Li.add(deo, nr + 1);
+    Li.add(dtries, nr, h->forest);
+    place(c->rv_in, Li);
+    if (roots32) HIPCHK(hipMemcpyAsync(droots, roots32, nr * 32, hipMemcpyHostToDevice, st));
+    if (origins32) HIPCHK(hipMemcpyAsync(dorig, origins32, nr * 32, hipMemcpyHostToDevice, st));
+    if (ne) HIPCHK(hipMemcpyAsync(dkeys, keys32 + 32 * e0, ne * 32, hipMemcpyHostToDevice, st));
+    if (vb) HIPCHK(hipMemcpyAsync(dvals, vals + v0, vb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dvoff, rvo.data(), (ne + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(deo, reo.data(), (nr + 1) * 8, hipMemcpyHostToDevice, st));
+    if (h->forest) HIPCHK(hipMemcpyAsync(dtries, tries, nr * 4, hipMemcpyHostToDevice, st));
+    fill_ranges_dev(h, h->forest ? dtries : nullptr, ht, roots32 ? droots : nullptr, origins32 ? dorig : nullptr, nr,
+                    dkeys, dvals, dvoff, deo, ne, status, stubs_left, n_keys, n_stubs);
   })
 }
 

@@ -255,12 +255,38 @@ class _Versioned:
     def fill(self, nodes):
         """Resolve the stubs whose node is among `nodes` ({hash: encoding} or a list of encodings;
         kh_trie_fill_nodes); returns the number of nodes decoded into the handle."""
+        if isinstance(nodes, ProofTable):
+            nodes = nodes.nodes
         encs = list(nodes.values()) if isinstance(nodes, dict) else list(nodes)
         ed, eo = _pack_dev(encs, self.dev)
         n = ctypes.c_uint64()
         self.ctx._sync()
         check(lib().kh_trie_fill_nodes(self.h, _ptr(ed), _ptr(eo), len(encs), ctypes.byref(n), None))
         return int(n.value)
+
+    def _fill_ranges(self, ranges, proof, forest):
+        """kh_trie_fill_ranges_host over ranges = [(trie, root or None, origin or None, (keys, vals))]:
+        -> (statuses, stubs_left, {"keys", "stubs"}).  A root of None is allowed only when no range
+        carries one (no claim)."""
+        ranges = [tuple(r) for r in ranges]
+        if proof is not None:
+            self.fill(proof)
+        roots = [r for _, r, _, _ in ranges]
+        if any(r is None for r in roots) and not all(r is None for r in roots):
+            raise _lib.MPTException(_lib.KH_EINVAL, "a root for every range, or for none")
+        claim = bool(roots) and roots[0] is not None
+        nr, _, a = _range_arrays(roots if claim else [b"\0" * 32] * len(ranges), [o for _, _, o, _ in ranges],
+                                 [e for _, _, _, e in ranges], None, None)
+        tb = np.asarray([t for t, _, _, _ in ranges] + [0], np.uint32) if forest else None
+        status, left = np.zeros(nr + 1, np.uint8), np.zeros(nr + 1, np.uint64)
+        nk, ns = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._sync()
+        check(lib().kh_trie_fill_ranges_host(self.h, _at(tb), a["roots"].ctypes.data if claim else None,
+                                             a["origins"].ctypes.data, nr, a["keys"].ctypes.data,
+                                             a["vals"].ctypes.data, a["voff"].ctypes.data, a["ent_off"].ctypes.data,
+                                             status.ctypes.data, left.ctypes.data, ctypes.byref(nk), ctypes.byref(ns)))
+        return ([int(x) for x in status[:nr]], [int(x) for x in left[:nr]],
+                {"keys": int(nk.value), "stubs": int(ns.value)})
 
     def _evict_subtrees(self, prefixes, trie_ids):
         from .codec import nibbles_to_path32
@@ -458,6 +484,18 @@ class ResidentTrie(_Versioned):
         status one of KH_EVICT_NONE / DONE / STUB / EMBEDDED, the hash the one to fetch to bring the
         subtree back (DONE, STUB); counters {evicted, keys, records}."""
         return self._evict_subtrees(prefixes, None)
+
+    def fill_range(self, origin, entries, proof=None):
+        """Take one range response into this partial trie (kh_trie_fill_ranges_host): entries =
+        (keys, vals) in key order, 32-byte TRIE keys (the kec256 values on a hash_keys trie), origin the
+        requested origin (None: zero).  proof (the response's boundary-proof nodes: a ProofTable, dict
+        or list) is given to fill() first.  The stubs inside [origin, last key] are replaced by the
+        subtrees built from the entries, kept only if the root does not move.  Returns (statuses,
+        stubs_left, counters): statuses = [KH_RANGE_*], stubs_left = [live stubs afterwards] (0: the
+        trie is whole), counters {"keys", "stubs"} gained / replaced; any status but KH_RANGE_OK
+        leaves the trie exactly as it was.  The sync loop: range -> fill proof -> fill range ->
+        continue from the last key + 1 while stubs_left > 0."""
+        return self._fill_ranges([(0, self.root, origin, entries)], proof, False)
 
     def _flag(self, hash_keys):
         """The trie's key encoder is fixed at open (as the reference's implicit
@@ -1181,6 +1219,16 @@ class ResidentForest(_Versioned):
         ResidentTrie.evict_subtrees.  (tries=None passes no trie array: the library refuses it.)"""
         q = list(prefixes)
         return self._evict_subtrees([p for _, p in q], [t for t, _ in q] if tries is not None else None)
+
+    def fill_ranges(self, ranges, proof=None):
+        """Take range responses into the forest, many in one call (kh_trie_fill_ranges_host): ranges =
+        [(trie_id, root, origin or None, (keys, vals))], a trie named once.  A trie the forest does
+        not hold is taken WHOLE from its entries (they must hash to root); a resident partial trie
+        has the stubs inside [origin, last key] replaced, root its current root (every root None: no
+        claim, resident tries only).  proof is given to fill() first.  All or nothing over the call;
+        returns (statuses, stubs_left, counters) as ResidentTrie.fill_range -- the GetStorageRanges
+        shape: many whole small tries and one tail."""
+        return self._fill_ranges(ranges, proof, True)
 
     def load_nodes(self, roots, nodes, partial=False):
         """Page tries in (kh_forest_load_nodes): roots {trie_id: root}, nodes {hash: encoding} or a
