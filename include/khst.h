@@ -905,6 +905,60 @@ int kh_dev_trie_diffs(kh_trie* a, const uint32_t* d_tries_a, kh_trie* b, const u
                       uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_done,
                       uint8_t next32[32], uint8_t missing32[32]);
 
+/* ---- changes since a savepoint: a block's key delta read from the undo journal, without a copy ----
+ * The keys whose entries differ between the version at an OPEN SAVEPOINT of handle h and its current
+ * version, with kinds and values, in (trie id, key) order: what kh_trie_diff_host /
+ * kh_trie_diffs_host give against a kh_trie_copy taken at the savepoint, read instead from the
+ * records the commits since journaled and appended.  Work and scratch follow those records (the
+ * keys a block changed and their paths), never the trie, and no second handle is held.
+ *   Versions.  level selects the savepoint: 0 the innermost, 1 .. depth that savepoint counted from
+ * the outermost (1: everything the journal holds).  S is the handle's content at that savepoint, C
+ * its content now -- after the commits, kh_block_commit calls and forest loads made since.  Content
+ * is a map (trie id, TRIE key) -> (value bytes, is-value-only-branch); a single trie is trie id 0.
+ *   Differences.  kh_trie_diff_host's, with a = S and b = C: a key in S only (KH_DIFF_ONLY_A), in C
+ * only (KH_DIFF_ONLY_B), or in both with different value bytes or where exactly one entry is a
+ * value-only branch (KH_DIFF_CHANGED).  Values are C's for kinds 2 and 3; kind 1 has an empty span.
+ * NOT differences: a key upserted with the bytes it had; a key deleted and put back with the same
+ * bytes, in one commit or across several; a key created and deleted again since the savepoint; a
+ * leaf that was only re-anchored because a sibling went and its branch collapsed.
+ *   KH_CHANGES_REVERSE swaps the roles, a = C and b = S: the kinds swap and the values are the
+ * savepoint's (still in the heap: it is append-only between compactions, and kh_trie_compact is
+ * refused while a savepoint is open).  These are the ops that undo the commits: a replica's reorg.
+ *   Answer.  The differences in ascending (trie id, key) order from (from_trie, from32) inclusive
+ * (from32 NULL: from the beginning; from_trie is ignored then, and on a single trie): at most
+ * max_entries, cut to the longest prefix whose values fit val_cap.  tries (nullable on a single
+ * trie: max_entries ids), keys32, kinds, vals and voff (max_entries + 1 slots) have the diff's
+ * layout.  *n_total (nullable) is the number of differences at or after the resume point, returned
+ * or not.  *more = 1 and (next_trie, next32) = the first difference not returned when one exists,
+ * else *more = 0.  There is no cursor: every call reads the journal again, so one call with
+ * max_entries >= *n_total is the cheap way to take a whole answer.
+ *   Read-only on the handle: root, records, last roots, write-back set, kh_trie_missing list, export
+ * cursors and the journal are as before.
+ *   Partial handles: the answer is exact and the call never returns KH_ENODE -- a commit creates and
+ * removes no stub, and stubs are not entries; nothing is walked, so nothing missing is met.  (A diff
+ * of two copies gives up where an unskipped stub lies on a changed path.)
+ *   KH_EINVAL  no savepoint open, level > depth, unknown flags, max_entries == 0 or >= 2^31, a null
+ *              handle or required output (tries on a forest)
+ *   KH_ENOSPC  not even the first difference's value fits: *val_bytes is its size and *n_total is
+ *              written; nothing else is written
+ * A handle whose in-flight commit tail failed refuses the call like every other.
+ * _host form with host buffers; kh_dev_trie_changes_since with tries / keys32 / kinds / vals / voff
+ * device buffers (voff 8-byte aligned), on the handle's context stream (the scalar outputs are host
+ * words, valid on return).  (khipu_amd/csrc/changes.h) */
+#define KH_CHANGES_REVERSE 0x1u
+int kh_trie_changes_since_host(kh_trie* h, uint32_t level, uint32_t flags,
+                               uint32_t from_trie, const uint8_t from32[32],
+                               uint64_t max_entries, uint64_t val_cap,
+                               uint32_t* tries, uint8_t* keys32, uint8_t* kinds, uint8_t* vals, uint64_t* voff,
+                               uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_total, int* more,
+                               uint32_t* next_trie, uint8_t next32[32]);
+int kh_dev_trie_changes_since(kh_trie* h, uint32_t level, uint32_t flags,
+                              uint32_t from_trie, const uint8_t from32[32],
+                              uint64_t max_entries, uint64_t val_cap,
+                              uint32_t* d_tries, uint8_t* d_keys32, uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff,
+                              uint64_t* n_entries, uint64_t* val_bytes, uint64_t* n_total, int* more,
+                              uint32_t* next_trie, uint8_t next32[32]);
+
 /* ---- range verification: range responses checked against a root, without a handle ----
  * The receiving half of kh_trie_range_host + kh_trie_prove(KH_PROVE_TRIE_KEYS) (snap's ranges,
  * geth's VerifyRangeProof), nr ranges a call over ONE node set.  Range s: root roots32[32s..),

@@ -1598,6 +1598,74 @@ JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_diff(JNIEnv* env, jclass cls, j
   return (jlong)ne;
 }
 
+/* The keys changed since an open savepoint of a resident trie or forest, read from its undo journal
+ * without a copy (kh_trie_changes_since_host): level 0 is the innermost savepoint, 1 .. depth that
+ * savepoint counted from the outermost.  The differences from (fromTrie, from) on (from byte[32] or
+ * null: from the beginning; fromTrie is read on forests only) go into the caller's arrays as diff's
+ * do -- side a the savepoint's version, side b the current one, and with reverse the other way
+ * round (the ops that undo the commits: a reorg) -- with tries (int per difference; may be null on a
+ * single trie) naming each difference's trie: at most min(keys.length / 32, kinds.length,
+ * voff.length - 1, tries.length) differences, with values fitting vals.  sizes[0] = differences,
+ * sizes[1] = value bytes, sizes[2] = 1 when a difference was not returned: next (byte[32]) is its
+ * key and sizes[4] its trie, the (fromTrie, from) of the next call; sizes[3] = the differences from
+ * (fromTrie, from) on, returned or not: one call sized from it takes them all.  Returns the count,
+ * or -1 when vals cannot hold even the first value (sizes[1] is its size, sizes[3] is set: grow and
+ * call again).  Exact on partial handles: never MPTNodeMissingException.  Region copies only, no
+ * critical region. */
+JNIEXPORT jlong JNICALL Java_khipu_trie_gpu_Khst_changesSince(JNIEnv* env, jclass cls, jlong handle, jint level,
+                                                             jboolean reverse, jint fromTrie, jbyteArray from,
+                                                             jintArray tries, jbyteArray keys, jbyteArray kinds,
+                                                             jbyteArray vals, jlongArray voff, jbyteArray next,
+                                                             jlongArray sizes) {
+  (void)cls;
+  if ((from && len_of(env, from) != 32) || len_of(env, next) < 32 || level < 0 || len_of(env, sizes) < 5) {
+    throw_cls(env, "java/lang/IllegalArgumentException",
+              "changesSince: from / next must hold 32 bytes, sizes 5 longs, level must not be negative");
+    return 0;
+  }
+  uint64_t max_entries = (uint64_t)len_of(env, keys) / 32;
+  const jsize nvo = len_of(env, voff);
+  if ((uint64_t)(nvo > 0 ? nvo - 1 : 0) < max_entries) max_entries = (uint64_t)(nvo > 0 ? nvo - 1 : 0);
+  if ((uint64_t)len_of(env, kinds) < max_entries) max_entries = (uint64_t)len_of(env, kinds);
+  if (tries && (uint64_t)len_of(env, tries) < max_entries) max_entries = (uint64_t)len_of(env, tries);
+  if (max_entries == 0) {
+    throw_cls(env, "java/lang/IllegalArgumentException", "changesSince: keys / kinds / voff / tries hold no difference");
+    return 0;
+  }
+  Bufs b = {0};
+  const uint8_t* fr = in_b(env, &b, from);
+  uint32_t* ts = out_buf(env, &b, tries, 4);
+  uint8_t* ks = out_buf(env, &b, keys, 1);
+  uint8_t* kd = out_buf(env, &b, kinds, 1);
+  uint8_t* vs = out_buf(env, &b, vals, 1);
+  uint64_t* vo = out_buf(env, &b, voff, 8);
+  if (bufs_failed(env, &b)) return 0;
+  uint64_t ne = 0, nb = 0, total = 0;
+  int more = 0;
+  uint32_t nt = 0;
+  uint8_t nx[32] = {0};
+  const int rc = kh_trie_changes_since_host(H(handle), (uint32_t)level, reverse ? KH_CHANGES_REVERSE : 0u,
+                                            (uint32_t)fromTrie, fr, max_entries, (uint64_t)len_of(env, vals), ts, ks, kd,
+                                            vs, vo, &ne, &nb, &total, &more, &nt, nx);
+  if (rc == KH_OK) {
+    put_i(env, tries, ts, ne);
+    put_b(env, keys, ks, 32 * ne);
+    put_b(env, kinds, kd, ne);
+    put_b(env, vals, vs, nb);
+    put_l(env, voff, vo, ne + 1);
+    if (more) put_b(env, next, nx, 32);
+  }
+  bufs_free(&b);
+  const jlong sz[5] = {(jlong)ne, (jlong)nb, (jlong)more, (jlong)total, (jlong)nt};
+  put_l(env, sizes, sz, 5);
+  if (rc == KH_ENOSPC) return -1;
+  if (rc != KH_OK) {
+    throw_kh(env, rc);
+    return 0;
+  }
+  return (jlong)ne;
+}
+
 /* Many trie pairs in one call (kh_trie_diffs_host): nq requests -- trie triesA[q] of handleA against
  * trie triesB[q] of handleB (the ids are read on forests only and may be null on a single trie;
  * triesB null: triesA, two versions of one forest), range [origins[32q..), limits[32q..)] (either

@@ -29,6 +29,7 @@ KH_PROVE_TRIE_KEYS = 0x2  # kh_trie_prove: the keys are trie keys already (a ran
 KH_DIFF_ONLY_A = 1   # the key is in a only: a delete on the way from a to b
 KH_DIFF_ONLY_B = 2   # the key is in b only: an upsert of b's value
 KH_DIFF_CHANGED = 3  # in both; values differ, or exactly one side is a value-only branch
+KH_CHANGES_REVERSE = 0x1  # kh_trie_changes_since_host: a = the current version, b = the savepoint's
 # kh_verify_proofs statuses
 KH_PROOF_ABSENT = 0     # valid: the key is not in the trie
 KH_PROOF_VALUE = 1      # valid: the value is returned
@@ -69,7 +70,7 @@ EXPORTS = (
     "kh_trie_missing", "kh_trie_need_host", "kh_trie_range_host", "kh_dev_trie_range", "kh_verify_ranges",
     "kh_dev_verify_ranges", "kh_trie_ranges_host", "kh_dev_trie_ranges", "kh_trie_diff_host", "kh_dev_trie_diff",
     "kh_trie_diffs_host", "kh_dev_trie_diffs", "kh_trie_evict_subtrees", "kh_trie_commit_witness_host",
-    "kh_trie_fill_ranges_host", "kh_dev_trie_fill_ranges",
+    "kh_trie_fill_ranges_host", "kh_dev_trie_fill_ranges", "kh_trie_changes_since_host", "kh_dev_trie_changes_since",
 )
 
 
@@ -238,6 +239,11 @@ def lib():
     L.kh_dev_trie_diffs.argtypes = L.kh_trie_diffs_host.argtypes
     L.khst_diffs_rounds.restype = u32  # (measurements: the last batched diff's rounds and selected items)
     L.khst_diffs_visited.restype = u64
+    L.kh_trie_changes_since_host.argtypes = [vp, u32, u32, u32, vp, u64, u64, vp, vp, vp, vp, vp, ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(i32),
+                                             ctypes.POINTER(u32), vp]
+    L.kh_dev_trie_changes_since.argtypes = L.kh_trie_changes_since_host.argtypes
+    L.khst_changes_sorts.restype = u32  # (measurements and tests: the radix sorts of the last changes-since call)
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int or name not in ("kh_last_error", "kh_version"):

@@ -1,7 +1,9 @@
 // kh_trie_range_host / kh_dev_trie_range and the batched kh_trie_ranges_host / kh_dev_trie_ranges:
 // their kernels (k_ranges_*: range.h holds the bodies of both); kh_trie_diff_host / kh_dev_trie_diff,
 // the same ordered frontier run over two tries in lockstep (diff.h: k_diff_*), and the batched
-// kh_trie_diffs_host / kh_dev_trie_diffs (k_diffs_*).  Every call launches kernels of its own; the
+// kh_trie_diffs_host / kh_dev_trie_diffs (k_diffs_*); kh_trie_changes_since_host /
+// kh_dev_trie_changes_since (changes.h: k_chg_*, changes_scan), which finds its differences in the
+// journal and pages them with the diff's tail.  Every call launches kernels of its own; the
 // host code that sequences them is one driver: run_rounds (the round loop), fit_page (the tail) and
 // page_to_host / page_in_place (the two forms of an entry point), the 16 words they share named by
 // TotWord.  range_scan, ranges_scan, diff_scan and diffs_scan hold what differs: the workspace,
@@ -12,7 +14,7 @@
 
 #include <cstdint>
 
-#include "diff.h"
+#include "changes.h"
 #include "host.h"
 
 using namespace khst;
@@ -353,6 +355,78 @@ __global__ void __launch_bounds__(BS) k_diffs_write(DSide A, DSide B, const uint
   df_write(A, ia[i], B, ib[i], i, pos[i], keys32, kinds, voff, vals);
 }
 
+// ---- changes since a savepoint (changes.h): candidates from the journal and the appended records,
+// sorted by (trie, key), joined a run a thread; the page is the trie diff's (k_diff_lens / _fit / _write)
+// Collect: one thread a journal position (its saved copy and the current record at its index) or an
+// appended record.  What decides -- live, db -- lies in ONE 16-byte word of a record (bytes 32..47),
+// so a thread loads that word and touches one line a record, as a record read whole would a lane;
+// the keys are read later, of the kept candidates only.
+__global__ void __launch_bounds__(BS) k_chg_collect(ChgSrc S, uint32_t* keep) {
+  const uint64_t g = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (g >= S.jn + S.an) return;
+  if (g < S.jn) {
+    const uint64_t p = S.j0 + g;
+    const uint32_t idx = S.jidx[p];
+    const ulonglong2 cw = *(const ulonglong2*)(S.J.rk.b + p * REC_BYTES + 32);
+    const bool old = chg_keep_old(idx, S.rn0, chg_entry_words(cw.x, cw.y));
+    bool cur = false;
+    if (old) {
+      const ulonglong2 rw = *(const ulonglong2*)(S.R.rk.b + (uint64_t)idx * REC_BYTES + 32);
+      cur = chg_keep_new(idx, S.rn0, true, chg_entry_words(rw.x, rw.y));
+    }
+    keep[g] = old ? 1u : 0u;
+    keep[S.jn + g] = cur ? 1u : 0u;
+  } else {
+    const uint64_t a = g - S.jn;
+    const ulonglong2 rw = *(const ulonglong2*)(S.R.rk.b + (S.rn0 + a) * REC_BYTES + 32);
+    keep[2 * S.jn + a] = chg_entry_words(rw.x, rw.y) ? 1u : 0u;
+  }
+}
+// the kept slots, in slot order (pos: the exclusive scan of keep)
+__global__ void __launch_bounds__(BS) k_chg_compact(const uint32_t* keep, const uint32_t* pos, uint64_t n,
+                                                    uint32_t* sv) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i < n && keep[i]) sv[pos[i]] = (uint32_t)i;
+}
+// word w of every slot's sort key, in the slots' present order (one stable radix sort a word)
+__global__ void __launch_bounds__(BS) k_chg_sortkey(ChgSrc S, const uint32_t* sv, uint64_t n, uint32_t w,
+                                                    uint64_t* ck) {
+  const uint64_t j = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (j < n) ck[j] = chg_sort_word(S, sv[j], w);
+}
+// Join: one thread a sorted place; the head of a run of equal (trie, key) classifies the run, and a
+// difference at or after the resume point (from.o; has_from) is flagged with its item.  *tie: the
+// order cannot be trusted (chg_head).
+__global__ void __launch_bounds__(BS) k_chg_join(ChgSrc S, const uint32_t* sv, uint64_t n, uint32_t reverse,
+                                                 uint32_t has_from, uint32_t from_trie, KeyRange from, uint32_t* ja,
+                                                 uint32_t* jb, uint32_t* flag, unsigned long long* tie) {
+  const uint64_t j = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (j >= n) return;
+  bool t = false;
+  uint32_t po, rn, f = 0;
+  if (chg_head(S, sv, j, &t) && chg_join(S, sv, n, j, &po, &rn) &&
+      (!has_from || chg_from(S, sv[j], from_trie, from.o))) {
+    chg_item(po, rn, reverse != 0, &ja[j], &jb[j]);
+    f = 1;
+  }
+  if (t) *tie = 1;
+  flag[j] = f;
+}
+// the first `cut` differences as items (dpos: the exclusive scan of flag)
+__global__ void __launch_bounds__(BS) k_chg_list(const uint32_t* flag, const uint32_t* dpos, uint64_t n, uint64_t cut,
+                                                 const uint32_t* ja, const uint32_t* jb, uint32_t* ia, uint32_t* ib) {
+  const uint64_t j = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (j >= n || !flag[j] || dpos[j] >= cut) return;
+  ia[dpos[j]] = ja[j];
+  ib[dpos[j]] = jb[j];
+}
+// the trie ids of the n1 items looked at
+__global__ void __launch_bounds__(BS) k_chg_tries(DSide A, DSide B, const uint32_t* ia, const uint32_t* ib,
+                                                  uint64_t n1, uint32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * BS + threadIdx.x;
+  if (i < n1) out[i] = chg_item_trie(A, ia[i], B, ib[i]);
+}
+
 // ---------------------------------------------------------------------------
 // host: the frontier driver the four services share (range.h, diff.h)
 // ---------------------------------------------------------------------------
@@ -408,6 +482,7 @@ struct Work {
 struct Page {
   const uint32_t *ia = nullptr, *ib = nullptr, *iq = nullptr;
   const uint64_t* pos = nullptr;
+  const DSide *A = nullptr, *B = nullptr;  // a diff over other record arrays than the handles' (changes_scan)
   uint64_t nq = 0;            // the requests of a batched call (0: a single call)
   uint64_t k = 0, bytes = 0;  // the things returned and their value bytes (k = 0: an empty answer)
   uint64_t n1 = 0;            // the things looked at: k < n1 when the answer is cut
@@ -535,8 +610,8 @@ static void page_write(kh_trie* a, kh_trie* b, const Page& P, uint8_t* d_keys32,
     hipLaunchKernelGGL(k_ranges_write, grid, dim3(BS), 0, st, recs_of(a), (const uint8_t*)a->heap.p, P.ia, P.iq, P.k,
                        P.pos, P.bytes, P.nq, d_keys32, d_voff, d_vals, d_ent_off);
   else if (!P.iq)
-    hipLaunchKernelGGL(k_diff_write, grid, dim3(BS), 0, st, side_of(a), side_of(b), P.ia, P.ib, P.k, P.pos, P.bytes,
-                       d_keys32, d_kinds, d_voff, d_vals);
+    hipLaunchKernelGGL(k_diff_write, grid, dim3(BS), 0, st, P.A ? *P.A : side_of(a), P.B ? *P.B : side_of(b), P.ia,
+                       P.ib, P.k, P.pos, P.bytes, d_keys32, d_kinds, d_voff, d_vals);
   else
     hipLaunchKernelGGL(k_diffs_write, grid, dim3(BS), 0, st, side_of(a), side_of(b), P.ia, P.ib, P.iq, P.k, P.pos,
                        P.bytes, P.nq, d_keys32, d_kinds, d_voff, d_vals, d_ent_off);
@@ -922,7 +997,190 @@ static int diffs_scan(kh_trie* a, const uint32_t* d_ta, kh_trie* b, const uint32
   return rc;
 }
 
+// ---------------------------------------------------------------------------
+// host: changes since a savepoint (changes.h)
+// ---------------------------------------------------------------------------
+static const Service CHANGES = {"changes since a savepoint", 0, "", ENOSPC_DIFF};
+// c->h_pinned past TotWord and PinWord: the call's own three words (ChgWord), the next pair's trie
+enum ChgPin : uint32_t { PIN_CHG = 24, PIN_NEXT_TRIE = 28 };
+enum ChgWord : uint32_t { CW_KEPT = 0, CW_TOTAL = 1, CW_TIE = 2, CW_WORDS = 4 };
+// the page of a call: the diff's page over the two record arrays, and the items' trie ids
+struct ChgPage {
+  Page P;
+  DSide A, B;
+  const uint32_t* d_tr = nullptr;
+  uint32_t next_trie = 0;
+};
+static uint32_t g_chg_sorts = 0;  // radix sorts of the last call (khst_changes_sorts: measurements and tests only)
+extern "C" uint32_t khst_changes_sorts() { return g_chg_sorts; }
+
+// The changes (changes.h) and the fit to val_cap, in the handle's gbuf on its stream: nothing but
+// that scratch is written.  KH_OK with the page in Q (Q.P.k = 0: no difference) and *n_entries,
+// *val_bytes, *n_total, *more, next32, Q.next_trie set; KH_ENOSPC with *val_bytes and *n_total.
+static int changes_scan(kh_trie* h, uint32_t level, bool reverse, uint32_t from_trie, const uint8_t* from32,
+                        uint64_t max_entries, uint64_t val_cap, ChgPage& Q, const PageOut& o, uint64_t* n_total,
+                        int* more) {
+  trie_settle(h);
+  if (h->sps.empty()) throw KhError{KH_EINVAL, "kh_trie_changes_since: no open savepoint"};
+  if (level > h->sps.size()) throw KhError{KH_EINVAL, "kh_trie_changes_since: level beyond the open savepoints"};
+  const Savepoint& sp = level ? *h->sps[level - 1] : *h->sps.back();
+  kh_ctx* c = h->c;
+  hipStream_t st = c->st;
+  const ChgSrc S{recs_at((uint8_t*)h->jrec.p), (const uint32_t*)h->jidx.p, recs_of(h), (const uint8_t*)h->heap.p,
+                 sp.jrec0,                     h->jrec_n - sp.jrec0,       sp.rn,      h->rn - sp.rn};
+  const uint64_t N = chg_slots(S);
+  if (N >= 0xFFFFFFFFull) throw KhError{KH_EINTERNAL, "kh_trie_changes_since: 2^32 candidates"};
+  Page& P = Q.P;
+  Q.A = chg_side(S, !reverse);
+  Q.B = chg_side(S, reverse);
+  P.A = &Q.A;
+  P.B = &Q.B;
+  g_chg_sorts = 0;
+  if (N == 0) {
+    *more = 0;
+    if (n_total) *n_total = 0;
+    *o.n_entries = *o.val_bytes = 0;
+    return KH_OK;
+  }
+  const uint64_t me = std::min(max_entries, N);  // (no more differences than candidates)
+  Layout L;
+  uint32_t *keep, *pos, *sv[2], *ja, *jb, *flag, *dpos, *ia, *ib, *tr;
+  uint64_t* ck[2];
+  void* rs;
+  unsigned long long* cw;
+  Work w;
+  L.add_all(N, keep, pos, sv[0], sv[1], ja, jb, flag, dpos, ck[0], ck[1]);
+  // (the sort is of the kept slots: fewer keys may take smaller tiles, and so more of them, than
+  // N would -- at most at 65536 keys, the largest sort with small tiles, prims.h RS_SMALL_N)
+  L.add(rs, std::max(radix_scratch_size(N), radix_scratch_size(std::min<uint64_t>(N, 65536))));
+  L.add_all(me + 2, ia, ib, tr, w.cnt);
+  L.add(w.scr, scan_scratch_size(std::max(N, me + 2) + 1, 8));
+  L.add(w.tot, T_WORDS);
+  L.add(cw, CW_WORDS);
+  place(h->gbuf, L);
+  // ---- collect, compact
+  HIPCHK(hipMemsetAsync(cw, 0, CW_WORDS * 8, st));
+  HIPCHK(hipMemsetAsync(w.tot, 0, T_WORDS * 8, st));
+  hipLaunchKernelGGL(k_chg_collect, GRID(S.jn + S.an, BS), dim3(BS), 0, st, S, keep);
+  LAUNCH_CHECK();
+  scan_u32(keep, pos, N, (uint32_t*)(cw + CW_KEPT), w.scr, st);
+  HIPCHK(hipMemcpyAsync(c->h_pinned + PIN_CHG, cw, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const uint64_t nc = c->h_pinned[PIN_CHG + CW_KEPT];
+  KeyRange from;
+  memset(&from, 0, sizeof(from));
+  if (from32) memcpy(from.o, from32, 32);
+  const bool has_from = from32 != nullptr;
+  const uint32_t ft = h->forest ? from_trie : 0u;
+  uint64_t nd = 0;
+  // ---- order, join: on the key's first word (and the trie id), again on all four after a tie
+  for (int full = 0; nc && full < 2; ++full) {
+    hipLaunchKernelGGL(k_chg_compact, GRID(N, BS), dim3(BS), 0, st, (const uint32_t*)keep, (const uint32_t*)pos, N,
+                       sv[0]);
+    LAUNCH_CHECK();
+    int cur = 0;
+    const uint32_t words[5] = {3, 2, 1, 0, CHG_WORD_TRIE};
+    for (int i = full ? 0 : 3; i < (h->forest ? 5 : 4); ++i) {
+      hipLaunchKernelGGL(k_chg_sortkey, GRID(nc, BS), dim3(BS), 0, st, S, (const uint32_t*)sv[cur], nc, words[i],
+                         ck[cur]);
+      LAUNCH_CHECK();
+      if (sort_pairs_u64(ck[cur], sv[cur], ck[cur ^ 1], sv[cur ^ 1], nc, 0, words[i] == CHG_WORD_TRIE ? 32 : 64, rs, st))
+        cur ^= 1;
+      ++g_chg_sorts;
+    }
+    hipLaunchKernelGGL(k_chg_join, GRID(nc, BS), dim3(BS), 0, st, S, (const uint32_t*)sv[cur], nc,
+                       (uint32_t)reverse, (uint32_t)has_from, ft, from, ja, jb, flag, cw + CW_TIE);
+    LAUNCH_CHECK();
+    scan_u32(flag, dpos, nc, (uint32_t*)(cw + CW_TOTAL), w.scr, st);
+    hipLaunchKernelGGL(k_chg_list, GRID(nc, BS), dim3(BS), 0, st, (const uint32_t*)flag, (const uint32_t*)dpos, nc,
+                       me + 1, (const uint32_t*)ja, (const uint32_t*)jb, ia, ib);
+    LAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(c->h_pinned + PIN_CHG, cw, CW_WORDS * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    nd = c->h_pinned[PIN_CHG + CW_TOTAL];
+    if (full || !c->h_pinned[PIN_CHG + CW_TIE]) break;  // (all four words sorted: neighbours may share the first)
+  }
+  if (n_total) *n_total = nd;
+  // ---- page: the trie diff's tail over the items
+  const DSide &A = Q.A, &B = Q.B;
+  const uint64_t ni = std::min(nd, me + 1);
+  if (ni) hipLaunchKernelGGL(k_chg_tries, GRID(ni, BS), dim3(BS), 0, st, A, B, (const uint32_t*)ia, (const uint32_t*)ib, ni, tr);
+  LAUNCH_CHECK();
+  P.ia = ia;
+  P.ib = ib;
+  P.pos = w.cnt;
+  Q.d_tr = tr;
+  const int rc = fit_page(
+      c, CHANGES, w, ni, me, h, h, P, o,
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diff_lens, GRID(n1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, nent, w.cnt,
+                           w.tot + T_STUB);
+      },
+      [&](uint64_t n1, uint64_t nent) {
+        hipLaunchKernelGGL(k_diff_fit, GRID(nent + 1, BS), dim3(BS), 0, st, A, B, P.ia, P.ib, n1, w.cnt, nent,
+                           (const uint64_t*)(w.tot + T_VALS), val_cap, w.tot + T_K, (uint64_t*)(w.tot + T_KEY));
+      });
+  if (rc != KH_OK) return rc;
+  *more = P.k < P.n1;
+  if (*more) {  // (the next pair's key came with the fit; its trie id is item k's)
+    HIPCHK(hipMemcpyAsync(c->h_pinned + PIN_NEXT_TRIE, tr + P.k, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    Q.next_trie = (uint32_t)c->h_pinned[PIN_NEXT_TRIE];
+  }
+  return rc;
+}
+static bool changes_args_ok(kh_trie* h, uint32_t flags, bool ptrs, uint64_t max_entries) {
+  if (!page_args_ok(h && ptrs, false, 0, max_entries)) return false;
+  return !(flags & ~(uint32_t)KH_CHANGES_REVERSE) || refuse("kh_trie_changes_since: unknown flags");
+}
+
 extern "C" {
+
+int kh_trie_changes_since_host(kh_trie* h, uint32_t level, uint32_t flags, uint32_t from_trie, const uint8_t from32[32],
+                               uint64_t max_entries, uint64_t val_cap, uint32_t* tries, uint8_t* keys32, uint8_t* kinds,
+                               uint8_t* vals, uint64_t* voff, uint64_t* n_entries, uint64_t* val_bytes,
+                               uint64_t* n_total, int* more, uint32_t* next_trie, uint8_t next32[32]) {
+  if (!changes_args_ok(h, flags, keys32 && kinds && voff && n_entries && val_bytes && more && next_trie && next32,
+                       max_entries))
+    return KH_EINVAL;
+  if (h->forest && !tries) return set_err(KH_EINVAL, "kh_trie_changes_since: a forest needs the tries output");
+  API_TRY({
+    HANDLE_LOCK(h);
+    HIPCHK(hipSetDevice(h->c->dev));
+    ChgPage Q;
+    const int rc = changes_scan(h, level, (flags & KH_CHANGES_REVERSE) != 0, from_trie, from32, max_entries, val_cap, Q,
+                                {n_entries, val_bytes, next32, nullptr}, n_total, more);
+    if (rc != KH_OK) return rc;
+    if (*more) *next_trie = Q.next_trie;
+    if (tries && Q.P.k)
+      HIPCHK(hipMemcpyAsync(tries, Q.d_tr, Q.P.k * 4, hipMemcpyDeviceToHost, h->c->st));  // (page_to_host syncs)
+    page_to_host(h, h, Q.P, keys32, kinds, vals, voff, nullptr);
+  })
+}
+
+int kh_dev_trie_changes_since(kh_trie* h, uint32_t level, uint32_t flags, uint32_t from_trie, const uint8_t from32[32],
+                              uint64_t max_entries, uint64_t val_cap, uint32_t* d_tries, uint8_t* d_keys32,
+                              uint8_t* d_kinds, uint8_t* d_vals, uint64_t* d_voff, uint64_t* n_entries,
+                              uint64_t* val_bytes, uint64_t* n_total, int* more, uint32_t* next_trie,
+                              uint8_t next32[32]) {
+  if (!changes_args_ok(h, flags, d_keys32 && d_kinds && d_voff && n_entries && val_bytes && more && next_trie && next32,
+                       max_entries))
+    return KH_EINVAL;
+  if (h->forest && !d_tries) return set_err(KH_EINVAL, "kh_trie_changes_since: a forest needs the tries output");
+  if (((uintptr_t)d_voff) & 7) return set_err(KH_EINVAL, "voff must be 8-byte aligned");
+  API_TRY({
+    HANDLE_LOCK(h);
+    HIPCHK(hipSetDevice(h->c->dev));
+    ChgPage Q;
+    const int rc = changes_scan(h, level, (flags & KH_CHANGES_REVERSE) != 0, from_trie, from32, max_entries, val_cap, Q,
+                                {n_entries, val_bytes, next32, nullptr}, n_total, more);
+    if (rc != KH_OK) return rc;
+    if (*more) *next_trie = Q.next_trie;
+    if (d_tries && Q.P.k)
+      HIPCHK(hipMemcpyAsync(d_tries, Q.d_tr, Q.P.k * 4, hipMemcpyDeviceToDevice, h->c->st));  // (page_in_place syncs)
+    page_in_place(h, h, Q.P, d_keys32, d_kinds, d_vals, d_voff, nullptr);
+  })
+}
 
 int kh_trie_diffs_host(kh_trie* a, const uint32_t* tries_a, kh_trie* b, const uint32_t* tries_b,
                        const uint8_t* origins32, const uint8_t* limits32, uint64_t nq, uint64_t max_entries,

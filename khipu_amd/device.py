@@ -171,6 +171,44 @@ class _Versioned:
     def _after_rollback(self):
         pass
 
+    def changes_since(self, level=0, reverse=False, start=None, max_entries=1024, val_cap=1 << 20):
+        """One page of the keys whose entries differ between the version at an open savepoint (level
+        0: the innermost; 1 .. depth: counted from the outermost) and the current version, read from
+        the journal without a copy (kh_trie_changes_since_host): (entries, more, next, n_total).
+        entries = [(key, kind, value)] in key order, on a forest [(trie, key, kind, value)] in (trie,
+        key) order, with the kinds of diff(): savepoint = side a, current = side b, and the current
+        values; reverse: the sides swapped and the savepoint's values (the ops that undo the commits).
+        start / next: a key, on a forest a (trie, key) pair; n_total counts the differences from start
+        on, returned or not.  KH_ENOSPC raises KhError with .val_bytes and .n_total."""
+        self.ctx._sync()
+        return trie_changes_since(self.h, isinstance(self, ResidentForest), level, reverse, start, max_entries, val_cap)
+
+    def changes_since_all(self, level=0, reverse=False):
+        """changes_since() in one call sized from n_total (val_cap grows on KH_ENOSPC): the (upserts,
+        deletes) of the commit that brings the savepoint's version to the current one (reverse: back),
+        upserts [(key, value)] and deletes [key], on a forest [(trie, key, value)] and [(trie, key)]."""
+        self.ctx._sync()
+        forest = isinstance(self, ResidentForest)
+        n, val_cap, start, ups, dels = 1024, 1 << 20, None, [], []
+        while True:
+            try:
+                ents, more, nxt, total = trie_changes_since(self.h, forest, level, reverse, start, n, val_cap)
+            except _lib.KhError as e:
+                if e.code != _lib.KH_ENOSPC:
+                    raise
+                n, val_cap = max(n, e.n_total), max(2 * val_cap, e.val_bytes)
+                continue
+            for e in ents:
+                if e[-2] == _lib.KH_DIFF_ONLY_A:
+                    dels.append(e[:-2] if forest else e[0])
+                else:
+                    ups.append(e[:-2] + e[-1:])
+            if not more:
+                return ups, dels
+            if len(ents) < n:  # (the values cut the page, not the entries)
+                val_cap *= 2
+            start, n = nxt, max(n, total - len(ents))
+
     def usage(self):
         """{records, live_records, heap_bytes, live_heap_bytes, map_slots, hbm_bytes} (kh_trie_usage)."""
         u = _lib.KhTrieUsage()
@@ -808,6 +846,41 @@ def trie_diff(ha, trie_a, hb, trie_b, origin=None, limit=None, max_entries=1024,
     return ([(o.keys[32 * i:32 * i + 32].tobytes(), int(o.kinds[i]),
               o.vals[int(o.voff[i]):int(o.voff[i + 1])].tobytes()) for i in range(k)], bool(o.more.value),
             o.nxt.tobytes() if o.more.value else None)
+
+
+def trie_changes_since(h, forest, level=0, reverse=False, start=None, max_entries=1024, val_cap=1 << 20):
+    """One page of kh_trie_changes_since_host (_Versioned.changes_since): (entries, more, next, n_total)."""
+    ft, fk = (start if forest else (0, start)) if start is not None else (0, None)
+    if fk is not None and len(fk) != 32:
+        raise _lib.MPTException(_lib.KH_EINVAL, "start is a 32-byte key")
+    fb = np.frombuffer(bytes(fk), np.uint8).copy() if fk is not None else None
+    o = _PageOut(max_entries, val_cap, kinds=True)
+    tries = np.zeros(len(o.kinds), np.uint32)
+    total, nt = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    rc = lib().kh_trie_changes_since_host(h, level, _lib.KH_CHANGES_REVERSE if reverse else 0, ft, _at(fb), o.n,
+                                          o.val_cap, _at(tries), _at(o.keys), _at(o.kinds), _at(o.vals), _at(o.voff),
+                                          ctypes.byref(o.ne), ctypes.byref(o.vb), ctypes.byref(total),
+                                          ctypes.byref(o.more), ctypes.byref(nt), _at(o.nxt))
+    try:
+        o.raise_for(rc)
+    except _lib.KhError as e:
+        if e.code == _lib.KH_ENOSPC:
+            e.n_total = int(total.value)
+        raise
+    k = int(o.ne.value)
+    ents = [(o.keys[32 * i:32 * i + 32].tobytes(), int(o.kinds[i]), o.vals[int(o.voff[i]):int(o.voff[i + 1])].tobytes())
+            for i in range(k)]
+    nxt = o.nxt.tobytes() if o.more.value else None
+    if forest:
+        ents = [(int(tries[i]),) + e for i, e in enumerate(ents)]
+        nxt = (int(nt.value), nxt) if o.more.value else None
+    return ents, bool(o.more.value), nxt, int(total.value)
+
+
+def changes_counters():
+    """The radix sorts of the last changes-since call (2 or more words: it fell back to the full-key
+    order): measurements and tests only."""
+    return int(lib().khst_changes_sorts())
 
 
 def _add_changes(ents, ups, dels):
