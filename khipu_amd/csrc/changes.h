@@ -4,7 +4,7 @@
 // of the handle, and work that follows the journal, not the trie.
 //
 //   what the journal holds   With a savepoint open, a commit saves every record it rewrites in place
-//             before the first change (k_rec_save, forest_commit step 5): the TOUCHED records (the
+//             before the first change (k_rec_save, Commit::journal_begin): the TOUCHED records (the
 //             leaves its ops end at: k_map_delete marks them dead; one that no op replaced or
 //             deleted is written again, live, by k_f_elem_recs) and the element sources that move
 //             (a subtree or leaf re-anchored because a sibling went or came: k_f_elem_recs rewrites

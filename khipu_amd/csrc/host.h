@@ -464,7 +464,7 @@ struct kh_trie {
   uint64_t map_epoch = 0;   // anchor-map rebuilds so far (a rebuild voids the slot log)
   bool flags_dirty = false; // a descent marked records and its commit did not finish
   DevBuf em_spare;          // the write-back buffer a savepoint's saved set rotates with
-  // a commit's tail left in flight (forest_commit, no write-back set): its records and anchor
+  // a commit's tail left in flight (Commit::early_roots, no write-back set): its records and anchor
   // map are written after the call returned; pend (pinned) gets the map's error flag and fresh
   // slot count, read by trie_settle before the host next needs them
   hipEvent_t ev_roots = nullptr, pend_ev = nullptr;

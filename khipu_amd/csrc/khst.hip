@@ -3692,11 +3692,21 @@ struct FCommit {  // one commit's inputs (device buffers)
   // refusal leaves its kind in *fill_refused (FILL_MISSING / FILL_MOVED).
   const FillMode* fill = nullptr;
   int* fill_refused = nullptr;
+  // the ops on the device; the other fields are the caller's to set
+  static FCommit of(const uint32_t* up_trie, const uint8_t* up_keys, const uint8_t* up_vals, const uint64_t* up_voff,
+                    uint64_t nup, const uint32_t* del_trie, const uint8_t* del_keys, uint64_t ndel, uint32_t klen) {
+    return FCommit{up_trie, up_keys, up_vals, up_voff, nup, del_trie, del_keys, ndel, klen};
+  }
 };
 
 static int emit_nodes_dev(kh_ctx* c, DevBuf& out, uint64_t* n_nodes, uint64_t* rlp_len);
 static void em_append(kh_ctx* c, DevBuf& em, uint64_t& tn, uint64_t& tb, const uint64_t* d_hashes, const uint8_t* src,
                       const std::vector<uint64_t>& list);
+__global__ void k_stub_missing(Recs R, const uint32_t* list, uint64_t n, uint64_t cap, uint32_t* out_trie,
+                               uint64_t* out_hash, unsigned long long* cnt);
+__global__ void k_stub_moved(Recs R, const uint32_t* sidx, const int8_t* pd, const uint32_t* src, const uint8_t* oldd,
+                             uint64_t m, uint64_t cap, uint32_t* out_trie, uint64_t* out_hash,
+                             unsigned long long* cnt);
 
 // a commit is about to replace the write-back set: the innermost savepoint keeps the set of its
 // version (once), and the commit writes into the spare buffer
@@ -3724,35 +3734,73 @@ JSeg khst::journal_reserve(kh_trie* h, uint64_t nrec, uint64_t nmap) {
   return s;
 }
 
-// One commit of a block's ops into the forest: upserts then deletes, the last op on a
-// key winning; deleting an absent key is a no-op.  Fills h->tries / h->roots.  A refused
-// batch (KH_EINVAL) leaves the handle as it was, its last roots and write-back set included;
-// with a savepoint open (h->sps) every change is journaled for kh_trie_rollback.
-__global__ void k_stub_missing(Recs R, const uint32_t* list, uint64_t n, uint64_t cap, uint32_t* out_trie,
-                               uint64_t* out_hash, unsigned long long* cnt);
-__global__ void k_stub_moved(Recs R, const uint32_t* sidx, const int8_t* pd, const uint32_t* src, const uint8_t* oldd,
-                             uint64_t m, uint64_t cap, uint32_t* out_trie, uint64_t* out_hash,
-                             unsigned long long* cnt);
 static const char* const MSG_STUB =
     "the commit needs a node the handle does not hold (MPTNodeMissingException): kh_trie_missing lists the hashes, "
     "kh_trie_fill_nodes takes the nodes; the trie is unchanged";
 
-static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
-  kh_ctx* c = h->c;
-  hipStream_t st = c->st;
+// One commit's state: what one stage of forest_commit (below, which shows their order) leaves for
+// a later one.  Whatever a single stage uses stays a local of that stage.
+namespace {
+struct Commit {
+  kh_trie* const h;
+  const FCommit& F;
+  kh_ctx* const c = h->c;
+  const hipStream_t st = c->st;
+  const uint64_t nops = F.nup + F.ndel;
+  const bool journal = !h->sps.empty();           // a savepoint is open
+  const bool defer = (bool)F.before_values;       // the values arrive late
+  const bool keep_em = h->flags & KH_EMIT_NODES;  // the handle hands out its write-back set
+  bool values_in = !defer;                        // the upserts' values are in the heap
+  bool rebuild = false, lazy = false;  // (early_roots) the map is rebuilt; the tail stays in flight
+  bool count_fresh = false;            // fctr[4] holds this commit's fresh map slots
+  // sort_ops: the sorted, distinct ops, their scans, the counts of its sync; the descent's touched
+  // list, the ops that make a value-only branch, and the commit's flags (fctr, zeroed by k_f_prep):
+  // [0] touched count, [1] replaced leaves, [2] anchor-map error, [3] refusal / map insert error,
+  // [4] fresh map slots, [5] element count, [6] value-only branches made, [7] the hashed ones
+  SortIO S{};
+  FOps O{};
+  uint32_t *tflag = nullptr, *tpos = nullptr, *ur = nullptr, *tlist = nullptr, nt = 0, nups = 0;
+  uint64_t *uoff = nullptr, nd = 0, ubytes = 0;
+  unsigned long long* fctr = nullptr;
+  uint8_t* vbf = nullptr;
+  // place_values: the trie list, roots and k_f_roots' final flags (back to back in h->tbuf), heap_n
+  // before the commit, the value offsets by upsert rank, the elements
+  uint32_t* tries = nullptr;
+  uint64_t *roots = nullptr, *uo = nullptr, hb = 0, ecap = 0;
+  unsigned long long* tail = nullptr;
+  size_t o_roots = 0, o_tail = 0;
+  Elems E{};
+  uint64_t ntl = 0, nrep = 0, ne = 0, nvb = 0;  // gather_elems: the counts of its sync
+  // value_branches: (encoding offset, length) of the hashed ones, for the write-back set
+  std::vector<uint64_t> vb_list;
+  DevBuf vbenc;
+  uint64_t* vbh = nullptr;
+  kh_stats bst{};  // build_elems: its stats, branches and elements
+  uint64_t B = 0, m = 0;
+  uint8_t *sel = nullptr, *hs = nullptr;  // the write-back selection (write_records); roots_to_host's pinned copy
+  bool begin(kh_stats* stats);  // the stages in order, then what more than one of them does
+  void sort_ops(), place_values(), descend(), gather_elems(), value_branches(), build_elems(), early_roots(),
+      values_now(), write_records(), write_back_set(), finish(kh_stats* stats);
+  void carve_elems(uint64_t ntl_cap), ops_post(bool meta, int copy), gather(bool redo), untouch(),
+      roots_kernel(bool results), roots_to_host();
+  template <class Launch>
+  void list_missing(uint64_t cap, Launch listing);
+  struct JLog { uint64_t *del = nullptr, *ins = nullptr; };
+  JLog journal_begin(const uint32_t* esrc, uint64_t ndel_log, uint64_t nins_log);
+};
+}  // namespace
+bool Commit::begin(kh_stats* stats) {  // false: an empty batch, done
   h->miss_tries.clear();
   h->miss_hashes.clear();
   if (F.inputs_ready) HIPCHK(hipStreamWaitEvent(st, F.inputs_ready, 0));
   if (stats) memset(stats, 0, sizeof(*stats));
-  const bool journal = !h->sps.empty();
-  const uint64_t nops = F.nup + F.ndel;
   ++h->epoch;  // (record indices may change from here on: an export cursor ends)
   if (nops == 0) {
     em_save(h);
     h->tries.clear();
     h->roots.clear();
     h->em_valid = false;
-    return;
+    return false;
   }
   if (nops >= (1ULL << 30)) throw KhError{KH_EINVAL, "batch too large"};
   if (!(h->flags & KH_HASH_KEYS) && F.klen != 32) throw KhError{KH_EINVAL, "keys must be 32 bytes unless KH_HASH_KEYS"};
@@ -3761,13 +3809,16 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   // commit's descent reads the map (done by now, stream order; a failure refuses the handle)
   trie_settle(h);
   HIPCHK(hipEventRecord(c->ev[6], st));
-  // ---- 1. op keys (the trie's key encoder), trie ids, sort by (trie, key), last op wins
+  return true;
+}
+// op keys (the trie's key encoder), trie ids, sort by (trie, key), last op wins; then the ops'
+// kinds, tries and value offsets.  Two syncs: the sort's, and the counts nt, nups, ubytes
+void Commit::sort_ops() {
   const bool segd = h->forest;
   Layout L;
-  uint64_t *K, *uoff, *ulen;
-  uint32_t *Tid, *tflag, *tpos, *isup, *ur;
+  uint64_t *K, *ulen;
+  uint32_t *Tid, *isup;
   uint8_t* kind;
-  SortIO S{};
   L.add(K, nops * 4);
   L.add(Tid, nops);
   S.declare(L, nops, nops * 4, true, nops, nops + 1, CTR_N);
@@ -3795,7 +3846,6 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       h->lo24_off == 0)
     S.rs_lo = 40;
   if (h->lo24_off) --h->lo24_off;
-  const bool defer = (bool)F.before_values;
   S.chk = defer ? nullptr : F.chk;
   if (segd && ((F.nup && !F.up_trie) || (F.ndel && !F.del_trie))) throw KhError{KH_EINVAL, "forest ops need trie ids"};
   // the op keys (unless hashed above) and trie ids, upserts then deletes: one launch
@@ -3811,34 +3861,26 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
                      (const uint64_t*)F.del_keys, F.ndel, copy_keys, segd ? F.up_trie : nullptr,
                      segd ? F.del_trie : nullptr, K, Tid, S.ctr);
   // the keys hashed (the trie's key encoder) and the composite sort keys made, one launch
-  {
-    const uint32_t* sg = segd ? Tid : nullptr;
-    unsigned long long* fl = S.ctr + CTR_TIE;
-    uint32_t* hdr = (uint32_t*)S.rs_scratch;
-    if (hk && F.klen <= 135)
-      hipLaunchKernelGGL((k_f_keys_ck<true, true>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys, F.ndel,
-                         F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
-    else if (hk)
-      hipLaunchKernelGGL((k_f_keys_ck<false, true>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys,
-                         F.ndel, F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
-    else
-      hipLaunchKernelGGL((k_f_keys_ck<true, false>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys,
-                         F.ndel, F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
-  }
+  const uint32_t* sg = segd ? Tid : nullptr;
+  unsigned long long* fl = S.ctr + CTR_TIE;
+  uint32_t* hdr = (uint32_t*)S.rs_scratch;
+  if (hk && F.klen <= 135)
+    hipLaunchKernelGGL((k_f_keys_ck<true, true>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys, F.ndel,
+                       F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
+  else if (hk)
+    hipLaunchKernelGGL((k_f_keys_ck<false, true>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys,
+                       F.ndel, F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
+  else
+    hipLaunchKernelGGL((k_f_keys_ck<true, false>), GRID(nops, BS), dim3(BS), 0, st, F.up_keys, F.nup, F.del_keys,
+                       F.ndel, F.klen, K, sg, S.sb, S.ck0, S.idx0, fl, hdr);
   LAUNCH_CHECK();
   S.ck_made = true;
   sort_dedup(c, S);
   if (S.fallback && S.rs_lo == 40) h->lo24_off = 16;
   if (!defer && F.chk && c->h_pinned[1] == F.chk_tok) throw KhError{KH_EINVAL, F.chk_msg};
-  const uint64_t nd = S.m;
+  nd = S.m;
   uint32_t* otrie = segd ? S.sseg : sseg;  // the compaction of duplicates moves the sorted ids
-  // the descent's touched list and the commit's flags (fctr, zeroed by k_f_prep): [0] touched
-  // count, [1] replaced leaves, [2] anchor-map error, [3] refusal / map insert error,
-  // [4] fresh map slots, [5] element count, [6] value-only branches made, [7] the hashed ones
   Layout L3;
-  uint32_t* tlist;
-  unsigned long long* fctr;
-  uint8_t* vbf;  // ops that make a value-only branch
   L3.add(tlist, nd * 70 + 16);
   L3.add(fctr, 8);
   L3.add(vbf, nd + 64);
@@ -3848,9 +3890,8 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   hipLaunchKernelGGL(k_f_prep, GRID(nd, BS), dim3(BS), 0, st, (const uint32_t*)S.sidx, nd, F.nup, segd, otrie,
                      F.up_voff, kind, tflag, isup, ulen, fctr);
   LAUNCH_CHECK();
-  FOps O{(const uint64_t*)S.skey, (const uint32_t*)otrie, (const uint8_t*)kind, nd};
-  uint32_t* ntp = (uint32_t*)(S.ctr + 12);
-  uint32_t* nupp = (uint32_t*)(S.ctr + 13);
+  O = FOps{(const uint64_t*)S.skey, (const uint32_t*)otrie, (const uint8_t*)kind, nd};
+  uint32_t *ntp = (uint32_t*)(S.ctr + 12), *nupp = (uint32_t*)(S.ctr + 13);
   if (nd <= SCAN_SMALL_MAX) {  // the three scans in one launch
     hipLaunchKernelGGL(k_scan_small3, dim3(3), dim3(SCAN_SMALL_THREADS), 0, st, ScanJob{tflag, tpos, ntp, false},
                        ScanJob{isup, ur, nupp, false}, ScanJob{ulen, uoff, S.ctr + 14, true}, nd);
@@ -3862,58 +3903,58 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
   }
   HIPCHK(hipMemcpyAsync(c->h_pinned, S.ctr + 12, 3 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  const uint32_t nt = (uint32_t)c->h_pinned[0], nups = (uint32_t)c->h_pinned[1];
-  const uint64_t ubytes = c->h_pinned[2];
-  // ---- trie list; upsert values into the heap (appended past heap_n, which moves only once
-  // the commit is accepted): uoff is the exclusive scan of their lengths over the sorted
-  // ops, uo the same offsets by upsert rank (uo[nups] = total)
+  nt = (uint32_t)c->h_pinned[0], nups = (uint32_t)c->h_pinned[1], ubytes = c->h_pinned[2];
+}
+// the elements' buffer for ntl_cap touched records: upserts, untouched children, kept leaves, roots
+void Commit::carve_elems(uint64_t ntl_cap) {
+  ecap = (uint64_t)nups + 16 * ntl_cap + nt + 16;
+  Layout Le;
+  E = Elems{};
+  Le.add(E.key, ecap * 4);
+  Le.add_all(ecap, E.seg, E.db);
+  Le.add(E.bref, ecap * 4);
+  Le.add_all(ecap, E.brl, E.vo, E.vl, E.src, E.oldd);
+  Le.add(E.cref, ecap * 4);
+  Le.add_all(ecap, E.crl, E.late);
+  Le.pad(64);
+  place(h->ebuf, Le);
+  E.n = fctr + 5;
+  E.cap = ecap;
+}
+// Room for the trie list and roots, the elements, and the upserts' values in the heap (past heap_n,
+// which moves once the commit is accepted: uoff is the exclusive scan of their lengths over the
+// sorted ops, uo the same offsets by upsert rank, uo[nups] = total).  Buffer growth only
+void Commit::place_values() {
   Layout Lt;
-  uint32_t* tries;
-  uint64_t* roots;
-  unsigned long long* tail;  // k_f_roots: the final flags
   Lt.add(tries, nt);
-  const size_t o_roots = Lt.add(roots, (uint64_t)nt * 4);
-  const size_t o_tail = Lt.add(tail, 8);
+  o_roots = Lt.add(roots, (uint64_t)nt * 4);
+  o_tail = Lt.add(tail, 8);
   place(h->tbuf, Lt);
   h->d_tries = tries;
   h->d_roots = roots;
   regrow(h->heap, h->heap_n, h->heap_n + ubytes + 64, st);
-  const uint64_t hb = h->heap_n;
+  hb = h->heap_n;
   h->ubuf.ensure(((uint64_t)nups + 1) * 8 + 64);
-  uint64_t* uo = (uint64_t*)h->ubuf.p;
-  // ---- the elements' buffer: upserts (values in the heap), untouched children, kept
-  // leaves, roots.  Sized from the last commit's touched count (or 4 per op) so the descent
-  // and the gather need no host round trip between them; a short buffer is grown to the
-  // exact size and gathered again after the one sync below.  (Touched records are live
-  // records: at most rn - rdead; a guess past 1M touched records -- 16M elements -- is left
-  // to the exact second pass.)
+  uo = (uint64_t*)h->ubuf.p;
+  // The elements' buffer is sized from the last commit's touched count (or 4 per op) so the
+  // descent and the gather need no host round trip between them; gather_elems grows a short one.
+  // (Touched records are live records: at most rn - rdead; a guess past 1M touched records --
+  // 16M elements -- is left to the exact second pass.)
   const uint64_t tl_cap = nd * 70 + 16;
   uint64_t ntl_guess = std::max<uint64_t>(4 * nd, h->ntl_hint + h->ntl_hint / 4);
   ntl_guess = std::min({ntl_guess, tl_cap, h->rn - h->rdead + 16, (uint64_t)1 << 20});
-  Elems E{};
-  auto carve_elems = [&](uint64_t ntl_cap) {
-    const uint64_t ecap = (uint64_t)nups + 16 * ntl_cap + nt + 16;
-    Layout Le;
-    E = Elems{};
-    Le.add(E.key, ecap * 4);
-    Le.add_all(ecap, E.seg, E.db);
-    Le.add(E.bref, ecap * 4);
-    Le.add_all(ecap, E.brl, E.vo, E.vl, E.src, E.oldd);
-    Le.add(E.cref, ecap * 4);
-    Le.add_all(ecap, E.crl, E.late);
-    Le.pad(64);
-    place(h->ebuf, Le);
-    E.n = fctr + 5;
-    E.cap = ecap;
-    return ecap;
-  };
-  uint64_t ecap = carve_elems(ntl_guess);
+  carve_elems(ntl_guess);
+}
+// k_f_ops_post: the trie list, the offsets by rank and the upserts' elements (meta); the values copied
+void Commit::ops_post(bool meta, int copy) {
   hipLaunchKernelGGL(k_f_ops_post, GRID(nd * CG, BS), dim3(BS), 0, st, O, (const uint32_t*)S.sidx, (const uint32_t*)ur,
                      F.up_vals, F.up_voff, (const uint64_t*)uoff, uo, (uint64_t)nups, ubytes, (uint8_t*)h->heap.p, hb,
-                     (const uint32_t*)tflag, (const uint32_t*)tpos, tries, E, true, !defer ? 1 : F.late ? 2 : 0,
-                     F.late);
+                     (const uint32_t*)tflag, (const uint32_t*)tpos, tries, E, meta, copy, F.late);
   LAUNCH_CHECK();
-  // ---- 2. descent: opened branches and touched leaves
+}
+// the descent: opened branches and touched leaves
+void Commit::descend() {
+  ops_post(true, !defer ? 1 : F.late ? 2 : 0);
   recs_reserve(h, h->rn + 16);
   if (h->mcap == 0) map_rebuild(h, nops + 1024);
   h->flags_dirty = true;  // until the touched records die (k_map_delete) or are untouched
@@ -3924,52 +3965,67 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     hipLaunchKernelGGL(k_f_descend, GRID(nd, BS), dim3(BS), 0, st, O, map_of(h), recs_of(h), (uint32_t*)h->touched.p,
                        (uint8_t*)h->replaced.p, tlist, fctr, vbf);
   LAUNCH_CHECK();
-  // ---- 3. elements: the gather (grid-stride over the device's touched count), one sync
-  auto gather = [&](bool redo) {
-    if (redo)  // the upserts' elements again, into the grown buffer
-      hipLaunchKernelGGL(k_f_upsert_elems, GRID(nd, BS), dim3(BS), 0, st, O, (const uint32_t*)tries, nt,
-                         (const uint32_t*)ur, (const uint64_t*)uo, E, hb, (uint64_t)nups, (const uint32_t*)S.sidx,
-                         F.late);
-    const uint64_t gblocks = std::min<uint64_t>((uint64_t)c->n_cu * KH_GATHER_PER_CU, (nd * 16 * 8 + GATHER_BS - 1) / GATHER_BS);
-    hipLaunchKernelGGL(k_f_gather, dim3((unsigned)std::max<uint64_t>(gblocks, 1)), dim3(GATHER_BS), 0, st, map_of(h),
-                       recs_of(h), (const uint32_t*)h->touched.p, (const uint8_t*)h->replaced.p,
-                       (const uint32_t*)tlist, (const unsigned long long*)fctr, (const uint32_t*)tries, nt, E, fctr);
+}
+// the elements gathered (grid-stride over the device's touched count), and fctr[0..6] read: one sync
+void Commit::gather(bool redo) {
+  if (redo)  // the upserts' elements again, into the grown buffer
+    hipLaunchKernelGGL(k_f_upsert_elems, GRID(nd, BS), dim3(BS), 0, st, O, (const uint32_t*)tries, nt,
+                       (const uint32_t*)ur, (const uint64_t*)uo, E, hb, (uint64_t)nups, (const uint32_t*)S.sidx, F.late);
+  const uint64_t gblocks = std::min<uint64_t>((uint64_t)c->n_cu * KH_GATHER_PER_CU, (nd * 16 * 8 + GATHER_BS - 1) / GATHER_BS);
+  hipLaunchKernelGGL(k_f_gather, dim3((unsigned)std::max<uint64_t>(gblocks, 1)), dim3(GATHER_BS), 0, st, map_of(h),
+                     recs_of(h), (const uint32_t*)h->touched.p, (const uint8_t*)h->replaced.p, (const uint32_t*)tlist,
+                     (const unsigned long long*)fctr, (const uint32_t*)tries, nt, E, fctr);
+  LAUNCH_CHECK();
+  HIPCHK(hipMemcpyAsync(c->h_pinned, fctr, 56, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+}
+// A refusal's missing list: `listing` launches the kernel that fills (tries, hashes, count), at
+// most cap of them, carved from h->selb; read into h->miss_tries / h->miss_hashes.  One sync
+template <class Launch>
+void Commit::list_missing(uint64_t cap, Launch listing) {
+  Layout Lm;
+  uint32_t* mt;
+  uint64_t* mh;
+  unsigned long long* mc;
+  Lm.add(mt, cap);
+  Lm.add(mh, cap * 4);
+  Lm.add(mc, 8);
+  place(h->selb, Lm);
+  HIPCHK(hipMemsetAsync(mc, 0, 8, st));
+  listing(mt, mh, mc);
+  LAUNCH_CHECK();
+  stub_missing_read(h, mt, mh, mc, cap);
+}
+// A refusal before any record or map write: the descent's flags cleared, the handle as it was
+void Commit::untouch() {
+  if (ntl) {
+    hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
+                       (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p);
     LAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(c->h_pinned, fctr, 56, hipMemcpyDeviceToHost, st));  // [0..6]
     HIPCHK(hipStreamSynchronize(st));
-  };
+  }
+  h->flags_dirty = false;
+}
+// The gather and its sync: ntl, nrep, ne, nvb.  A batch the descent refused ends here, the handle
+// untouched; a buffer guessed too small is carved to the exact size and gathered again (one more sync).
+void Commit::gather_elems() {
   gather(false);
-  const uint64_t ntl = c->h_pinned[0], nrep = c->h_pinned[1];
+  ntl = c->h_pinned[0], nrep = c->h_pinned[1];
   if (c->h_pinned[2] == 3) throw KhError{KH_EINTERNAL, "forest descent: corrupt anchor map"};
   if (c->h_pinned[3]) {  // nothing has changed yet: clear the descent's flags and refuse the batch
     const bool stub = (c->h_pinned[3] & 2) != 0;
     if (stub) {  // every stub an op reached is in the touched list, once: the hashes to fetch
-      Layout Lm;
-      uint32_t* mt;
-      uint64_t* mh;
-      unsigned long long* mc;
-      Lm.add(mt, ntl);
-      Lm.add(mh, ntl * 4);
-      Lm.add(mc, 8);
-      place(h->selb, Lm);
-      HIPCHK(hipMemsetAsync(mc, 0, 8, st));
-      if (F.fill)  // (the inside stubs the descent dropped are in the list too: not missing)
-        hipLaunchKernelGGL(k_fill_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), *F.fill, (const uint32_t*)tlist,
-                           ntl, ntl, mt, mh, mc);
-      else
-        hipLaunchKernelGGL(k_stub_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)tlist, ntl,
-                           ntl, mt, mh, mc);
-      LAUNCH_CHECK();
-      stub_missing_read(h, mt, mh, mc, ntl);
+      list_missing(ntl, [&](uint32_t* mt, uint64_t* mh, unsigned long long* mc) {
+        if (F.fill)  // (the inside stubs the descent dropped are in the list too: not missing)
+          hipLaunchKernelGGL(k_fill_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), *F.fill,
+                             (const uint32_t*)tlist, ntl, ntl, mt, mh, mc);
+        else
+          hipLaunchKernelGGL(k_stub_missing, GRID(ntl, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)tlist, ntl,
+                             ntl, mt, mh, mc);
+      });
       if (F.fill_refused) *F.fill_refused = FILL_MISSING;
     }
-    if (ntl) {
-      hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
-                         (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p);
-      LAUNCH_CHECK();
-      HIPCHK(hipStreamSynchronize(st));
-    }
-    h->flags_dirty = false;
+    untouch();
     if (stub) throw KhError{KH_ENODE, MSG_STUB};
     throw KhError{KH_EINVAL,
                   "remove of a key held by a value-only branch: khipu's fix of the emptied branch throws "
@@ -3977,35 +4033,29 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
                   "is unchanged"};
   }
   if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "forest gather: corrupt anchor map"};
-  uint64_t ne = c->h_pinned[5];
+  ne = c->h_pinned[5];
   if (ne > ecap) {  // the guess was short: the exact capacity, gathered again
-    ecap = carve_elems(ntl);
+    carve_elems(ntl);
     gather(true);
     ne = c->h_pinned[5];
     if (c->h_pinned[2]) throw KhError{KH_EINTERNAL, "forest gather: corrupt anchor map"};
   }
   if (ne > ecap) throw KhError{KH_EINTERNAL, "forest gather: element overflow"};
-  // deferred values: once their producer is done (the host waits for its event to be recorded,
-  // the stream for the event), the values into the heap -- right before the element build's
-  // leaves read them, so the element sort and topology run beside the producer too
-  bool values_in = !defer;
-  auto values_now = [&] {
-    if (values_in) return;
-    values_in = true;
-    F.before_values();
-    if (F.vals_ready) HIPCHK(hipStreamWaitEvent(st, F.vals_ready, 0));
-    hipLaunchKernelGGL(k_f_ops_post, GRID(nd * CG, BS), dim3(BS), 0, st, O, (const uint32_t*)S.sidx,
-                       (const uint32_t*)ur, F.up_vals, F.up_voff, (const uint64_t*)uoff, uo, (uint64_t)nups, ubytes,
-                       (uint8_t*)h->heap.p, hb, (const uint32_t*)tflag, (const uint32_t*)tpos, tries, E, false,
-                       F.late ? 3 : 1, F.late);
-    LAUNCH_CHECK();
-  };
-  // value-only branches (rare: a re-put of a key sharing 63 nibbles with another): their
-  // encodings need the values, so a deferred producer is waited for here
-  const uint64_t nvb = c->h_pinned[6];
-  std::vector<uint64_t> vb_list;  // (encoding offset, length) of the hashed ones
-  DevBuf vbenc;
-  uint64_t* vbh = nullptr;
+  nvb = c->h_pinned[6];
+}
+// deferred values: once their producer is done (the host waits for its event to be recorded,
+// the stream for the event), the values into the heap -- right before the element build's
+// leaves read them, so the element sort and topology run beside the producer too
+void Commit::values_now() {
+  if (values_in) return;
+  values_in = true;
+  F.before_values();
+  if (F.vals_ready) HIPCHK(hipStreamWaitEvent(st, F.vals_ready, 0));
+  ops_post(false, F.late ? 3 : 1);
+}
+// value-only branches (rare: a re-put of a key sharing 63 nibbles with another): their encodings
+// need the values, so a deferred producer is waited for here; with a write-back set, one sync
+void Commit::value_branches() {
   if (nvb) {
     values_now();
     vbenc.ensure(ubytes + 32 * (uint64_t)nups + 64 + nvb * 48 + 64);
@@ -4024,15 +4074,16 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       if (nh) HIPCHK(hipMemcpy(vb_list.data(), vbl, 16 * nh, hipMemcpyDeviceToHost));
     }
   }
+}
+// The batch is accepted so far (the hint and the heap move); the element build (every touched
+// trie a segment; none when all tries were emptied) gives B branches over m elements.  A handle
+// with stubs checks the new topology: one sync, the last refusal that leaves the handle untouched.
+void Commit::build_elems() {
   h->ntl_hint = ntl;
   h->heap_n = hb + ubytes;
   HIPCHK(hipEventRecord(c->ev[7], st));
-  // ---- 4. element build (every touched trie a segment), or all tries emptied
-  BuildOut O2;
-  kh_stats bst{};
-  uint64_t B = 0, m = 0;
-  const bool keep_em = h->flags & KH_EMIT_NODES;
   if (ne) {
+    BuildOut O2;
     ElemArgs EA{E.db, E.bref, E.brl, E.oldd, E.cref, E.crl, (defer && F.late) ? E.late : nullptr, &h->elout, &h->eloutb};
     // encodings are kept (emit path) only when the handle hands out its write-back set;
     // otherwise the fused branch levels (one launch per level, no message arena)
@@ -4041,106 +4092,99 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     A.vlen = E.vl;
     A.el = &EA;
     A.dev_results = true;  // the counters come back with the roots (build_stats below)
-    if (defer) A.before_leaves = values_now;
+    if (defer) A.before_leaves = [this] { values_now(); };
     if (defer) A.late_ready = F.late_ready;
     run_build(c, A, O2, &bst);
     B = c->last_B;
     m = c->T.m;
     if (m != ne) throw KhError{KH_EINTERNAL, "forest: duplicate elements"};
-    // a handle that holds stubs: one whose anchor would move (a delete left it its parent's only
-    // child) is a missing node too, seen only now that the topology is known.  One more sync,
-    // before any record or map write; a handle without stubs never comes here.
+    // a stub whose anchor would move (a delete left it its parent's only child) is a missing node
+    // too, seen only now that the topology is known.  One more sync, before any record or map write
     if (h->nstubs) {
-      Layout Lm;
-      uint32_t* mt;
-      uint64_t* mh;
-      unsigned long long* mc;
       const uint64_t mcap = std::min<uint64_t>(m, h->nstubs);
-      Lm.add(mt, mcap);
-      Lm.add(mh, mcap * 4);
-      Lm.add(mc, 8);
-      place(h->selb, Lm);
-      HIPCHK(hipMemsetAsync(mc, 0, 8, st));
-      hipLaunchKernelGGL(k_stub_moved, GRID(m, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)c->T.sidx,
-                         (const int8_t*)c->T.lf_pd, (const uint32_t*)E.src, (const uint8_t*)E.oldd, m, mcap, mt, mh, mc);
-      LAUNCH_CHECK();
-      stub_missing_read(h, mt, mh, mc, mcap);
-      if (!h->miss_tries.empty()) {  // nothing has changed yet: as the descent's refusal above
-        if (ntl) {
-          hipLaunchKernelGGL(k_f_untouch, GRID(ntl, BS), dim3(BS), 0, st, (const uint32_t*)tlist, ntl,
-                             (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p);
-          LAUNCH_CHECK();
-          HIPCHK(hipStreamSynchronize(st));
-        }
-        h->flags_dirty = false;
+      list_missing(mcap, [&](uint32_t* mt, uint64_t* mh, unsigned long long* mc) {
+        hipLaunchKernelGGL(k_stub_moved, GRID(m, BS), dim3(BS), 0, st, recs_of(h), (const uint32_t*)c->T.sidx,
+                           (const int8_t*)c->T.lf_pd, (const uint32_t*)E.src, (const uint8_t*)E.oldd, m, mcap, mt, mh,
+                           mc);
+      });
+      if (!h->miss_tries.empty()) {  // nothing has changed yet: as the descent's refusal
+        untouch();
         h->heap_n = hb;  // (the upserts' values past it are dropped)
         if (F.fill_refused) *F.fill_refused = FILL_MOVED;
         throw KhError{KH_ENODE, MSG_STUB};
       }
     }
   }
-  // Without a write-back set or a map rebuild, the commit returns as soon as its roots are on
-  // the host; the records and the anchor map follow on the stream (the next call is ordered
-  // after them, trie_settle reads their flags): configs[2]'s account phase ends 0.1 ms sooner
-  const bool rebuild = ne && 2 * (h->mused + B + m + 1024) > h->mcap;
-  const bool lazy = ne && !keep_em && !rebuild;
-  uint8_t* hs = nullptr;
-  if (ne && (lazy || F.after_roots)) {  // the roots now (k_f_roots runs again with the final flags below)
-    hipLaunchKernelGGL(k_f_roots, GRID(nt, BS), dim3(BS), 0, st, (const uint64_t*)c->T.res_hash,
-                       (const uint32_t*)c->T.res_len, nt, roots, (const unsigned long long*)c->T.ctr,
-                       (const unsigned long long*)fctr, tail);
-    LAUNCH_CHECK();
-    if (F.after_roots) F.after_roots(st, nt);
-    if (lazy) {
-      if (!h->ev_roots) HIPCHK(hipEventCreateWithFlags(&h->ev_roots, hipEventDisableTiming));
-      if (!h->pend_ev) HIPCHK(hipEventCreateWithFlags(&h->pend_ev, hipEventDisableTiming));
-      if (!h->pend) HIPCHK(hipHostMalloc((void**)&h->pend, 64, hipHostMallocDefault));
-      hs = pinned_stage(c, o_tail + 64);
-      HIPCHK(hipMemcpyAsync(hs, tries, o_tail + 64, hipMemcpyDeviceToHost, st));
-      if (defer && F.chk) HIPCHK(hipMemcpyAsync(c->h_pinned + 8, F.chk, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(h->ev_roots, st));
-    }
+}
+// k_f_roots: the roots (of the element build's results; with none, every trie of the batch was
+// emptied) and the final flags after them
+void Commit::roots_kernel(bool results) {
+  const Topo& T = c->T;
+  hipLaunchKernelGGL(k_f_roots, GRID(nt, BS), dim3(BS), 0, st, results ? (const uint64_t*)T.res_hash : nullptr,
+                     results ? (const uint32_t*)T.res_len : nullptr, nt, roots,
+                     results ? (const unsigned long long*)T.ctr : nullptr, (const unsigned long long*)fctr, tail);
+  LAUNCH_CHECK();
+}
+// the trie list, the roots and the flags after them (carved back to back: one copy) to the pinned
+// staging (a pageable destination pins its pages on every copy), with a deferred producer's error word
+void Commit::roots_to_host() {
+  hs = pinned_stage(c, o_tail + 64);
+  HIPCHK(hipMemcpyAsync(hs, tries, o_tail + 64, hipMemcpyDeviceToHost, st));
+  if (defer && F.chk) HIPCHK(hipMemcpyAsync(c->h_pinned + 8, F.chk, 8, hipMemcpyDeviceToHost, st));
+}
+// Without a write-back set or a map rebuild, the commit returns as soon as its roots are on
+// the host; the records and the anchor map follow on the stream (the next call is ordered
+// after them, trie_settle reads their flags): configs[2]'s account phase ends 0.1 ms sooner.
+// Such a lazy commit, and one with F.after_roots, runs the roots kernel right after the build.
+void Commit::early_roots() {
+  rebuild = ne && 2 * (h->mused + B + m + 1024) > h->mcap;
+  lazy = ne && !keep_em && !rebuild;
+  if (!(ne && (lazy || F.after_roots))) return;
+  roots_kernel(true);  // (it runs again with the final flags in write_records, unless lazy)
+  if (F.after_roots) F.after_roots(st, nt);
+  if (lazy) {
+    if (!h->ev_roots) HIPCHK(hipEventCreateWithFlags(&h->ev_roots, hipEventDisableTiming));
+    if (!h->pend_ev) HIPCHK(hipEventCreateWithFlags(&h->pend_ev, hipEventDisableTiming));
+    if (!h->pend) HIPCHK(hipHostMalloc((void**)&h->pend, 64, hipHostMallocDefault));
+    roots_to_host();
+    HIPCHK(hipEventRecord(h->ev_roots, st));
   }
-  values_now();  // (no element build: the producer still finishes before the commit does)
-  // ---- 5. records: new branches, re-anchored / new elements; the anchor map follows
+}
+// journal (a savepoint is open): the records rewritten in place -- the touched ones and the
+// element sources that move (k_f_elem_recs leaves every other source record as it is) -- saved
+// before the first change; the map deletes' and inserts' slot logs.
+// The segment is listed before the first change, so a failure past it still rolls back.
+Commit::JLog Commit::journal_begin(const uint32_t* esrc, uint64_t ndel_log, uint64_t nins_log) {
+  if (!journal) return {};
+  JSeg js = journal_reserve(h, ntl + m, ndel_log + nins_log);
+  js.dpos = h->jmap_n;
+  js.dn = ndel_log;
+  js.ipos = js.dpos + ndel_log;
+  js.in = 0;  // set once the inserts are launched
+  const uint64_t nsave = ntl + m;
+  if (nsave)
+    hipLaunchKernelGGL(k_rec_save, GRID(nsave * 8, BS), dim3(BS), 0, st, (const uint8_t*)h->recs.p,
+                       (const uint32_t*)tlist, ntl, esrc, m, (uint32_t*)h->jidx.p + js.rpos,
+                       (uint8_t*)h->jrec.p + js.rpos * REC_BYTES);
+  LAUNCH_CHECK();
+  h->jsegs.push_back(js);
+  h->jrec_n += nsave;
+  h->jmap_n += ndel_log + nins_log;
+  return {(uint64_t*)h->jmap.p + 3 * js.dpos, (uint64_t*)h->jmap.p + 3 * js.ipos};
+}
+// records: new branches, re-anchored / new elements, the touched ones dead; then the anchor map.
+// No sync: a lazy commit leaves the map's flags to trie_settle, any other runs the roots kernel again
+void Commit::write_records() {
   const uint64_t nnew = nups;  // every upsert is a new leaf record
   recs_reserve(h, h->rn + B + nnew + 16);
   const uint64_t base_b = h->rn, base_e = h->rn + B;
   Recs R = recs_of(h);
   AMap M = map_of(h);
-  bool count_fresh = false;  // fctr[4] holds this commit's fresh map slots
-  uint32_t *isnew = nullptr, *nrank = nullptr, *eid = nullptr, *esrc = nullptr;
-  uint8_t* sel = nullptr;
-  // journal (a savepoint is open): the records rewritten in place -- the touched ones and the
-  // element sources -- saved before the first change; the map deletes' and inserts' slot logs.
-  // The segment is listed before the first change, so a failure past it still rolls back.
-  uint64_t *dlog = nullptr, *ilog = nullptr;
-  auto journal_begin = [&](uint64_t ndel_log, uint64_t nins_log) {
-    if (!journal) return;
-    JSeg js = journal_reserve(h, ntl + m, ndel_log + nins_log);
-    js.dpos = h->jmap_n;
-    js.dn = ndel_log;
-    js.ipos = js.dpos + ndel_log;
-    js.in = 0;  // set once the inserts are launched
-    // (the records rewritten in place: the touched ones and the element sources that move --
-    // k_f_elem_recs leaves every other source record as it is)
-    const uint64_t nsave = ntl + m;
-    if (nsave)
-      hipLaunchKernelGGL(k_rec_save, GRID(nsave * 8, BS), dim3(BS), 0, st, (const uint8_t*)h->recs.p,
-                         (const uint32_t*)tlist, ntl, (const uint32_t*)esrc, m, (uint32_t*)h->jidx.p + js.rpos,
-                         (uint8_t*)h->jrec.p + js.rpos * REC_BYTES);
-    LAUNCH_CHECK();
-    dlog = (uint64_t*)h->jmap.p + 3 * js.dpos;
-    ilog = (uint64_t*)h->jmap.p + 3 * js.ipos;
-    h->jsegs.push_back(js);
-    h->jrec_n += nsave;
-    h->jmap_n += ndel_log + nins_log;
-  };
   if (ne) {
     Layout Ls;
     uint8_t* rein;
     void* sscr;
-    uint32_t* tot;
+    uint32_t *tot, *isnew, *nrank, *eid, *esrc;
     Ls.add(sel, m + 2 * B);
     Ls.add_all(m, rein, isnew, nrank, eid, esrc);
     Ls.add(sscr, scan_scratch_bytes(m + 1, 4));
@@ -4159,10 +4203,10 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       hipLaunchKernelGGL(k_fill_sel, GRID(m + B, BS), dim3(BS), 0, st, T, E, (const uint32_t*)tries, M, R, B, sel);
       LAUNCH_CHECK();
     }
-    journal_begin(ntl + m, B + m);
+    const JLog jl = journal_begin(esrc, ntl + m, B + m);
     // old anchors out of the map (touched records, element sources), then touched records die
     hipLaunchKernelGGL(k_map_delete, GRID(ntl + m, BS), dim3(BS), 0, st, M, R, (const uint32_t*)tlist, ntl,
-                       (const uint32_t*)esrc, m, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p, dlog);
+                       (const uint32_t*)esrc, m, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p, jl.del);
     LAUNCH_CHECK();
     h->flags_dirty = false;
     hipLaunchKernelGGL(k_f_elem_recs, GRID(m, BS), dim3(BS), 0, st, T, E, (const uint32_t*)tries,
@@ -4176,9 +4220,9 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       // (the table's load grows by the inserts that took an empty slot: fctr[4], read at the
       // final sync; B + m bounds it for the rebuild test above)
       hipLaunchKernelGGL(k_map_insert, GRID(B + m, BS), dim3(BS), 0, st, M, R, base_b, B, (const uint32_t*)eid, m,
-                         fctr + 3, fctr + 4, ilog);
+                         fctr + 3, fctr + 4, jl.ins);
       LAUNCH_CHECK();
-      if (ilog) h->jsegs.back().in = B + m;
+      if (jl.ins) h->jsegs.back().in = B + m;
       count_fresh = true;
     }
     if (lazy) {  // the map's flags to the handle's pinned word pair, read by trie_settle
@@ -4187,25 +4231,22 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
       h->pend_valid = true;
       h->pend_fresh = count_fresh;
     } else {
-      hipLaunchKernelGGL(k_f_roots, GRID(nt, BS), dim3(BS), 0, st, (const uint64_t*)T.res_hash,
-                         (const uint32_t*)T.res_len, nt, roots, (const unsigned long long*)T.ctr,
-                         (const unsigned long long*)fctr, tail);
-      LAUNCH_CHECK();
+      roots_kernel(true);
     }
   } else {
-    journal_begin(ntl, 0);
+    const JLog jl = journal_begin(nullptr, ntl, 0);
     if (ntl)
       hipLaunchKernelGGL(k_map_delete, GRID(ntl, BS), dim3(BS), 0, st, M, R, (const uint32_t*)tlist, ntl,
                          (const uint32_t*)nullptr, (uint64_t)0, (uint32_t*)h->touched.p, (uint8_t*)h->replaced.p,
-                         dlog);
+                         jl.del);
     h->flags_dirty = false;
-    hipLaunchKernelGGL(k_f_roots, GRID(nt, BS), dim3(BS), 0, st, (const uint64_t*)nullptr, (const uint32_t*)nullptr,
-                       nt, roots, (const unsigned long long*)nullptr, (const unsigned long long*)fctr, tail);
-    LAUNCH_CHECK();
+    roots_kernel(false);
   }
   h->rn = base_e + nnew;
   h->nleaves = h->nleaves + nups - nrep;
-  // ---- 6. this commit's write-back set (kept on the device for kh_trie_emit_nodes)
+}
+// this commit's write-back set (kept on the device for kh_trie_emit_nodes)
+void Commit::write_back_set() {
   em_save(h);
   if (keep_em && ne) {
     c->T.emit_sel = sel;
@@ -4220,19 +4261,16 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     h->em_n = h->em_bytes = 0;
     h->em_valid = true;
   }
-  // ---- roots to the host
-  // (through the pinned staging: a pageable destination pins its pages on every copy)
-  // One sync: the trie list and roots (carved back to back), the element build's counters
-  // and the map's error flag.
+}
+// roots to the host, and the stats.  One sync: the trie list and roots, the element build's
+// counters and the map's error flag (a lazy commit waits for early_roots' copy only)
+void Commit::finish(kh_stats* stats) {
   h->tries.resize(nt);
   h->roots.resize((uint64_t)nt * 32);
-  // (k_f_roots left the final flags in the tail after the roots: one copy)
   if (lazy) {
     HIPCHK(hipEventSynchronize(h->ev_roots));
   } else {
-    hs = pinned_stage(c, o_tail + 64);
-    HIPCHK(hipMemcpyAsync(hs, tries, o_tail + 64, hipMemcpyDeviceToHost, st));
-    if (defer && F.chk) HIPCHK(hipMemcpyAsync(c->h_pinned + 8, F.chk, 8, hipMemcpyDeviceToHost, st));
+    roots_to_host();
     HIPCHK(hipStreamSynchronize(st));
   }
   // a deferred producer's error word, read at the last sync: the commit has changed the handle
@@ -4255,6 +4293,26 @@ static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
     stats->t_sort_ms = merge_ms;  // batch sort + descent + element gather
     stats->t_total_ms += merge_ms;
   }
+}
+// One commit of a block's ops into the forest: upserts then deletes, the last op on a
+// key winning; deleting an absent key is a no-op.  Fills h->tries / h->roots.  A refused
+// batch (KH_EINVAL, KH_ENODE) leaves the handle as it was, its last roots and write-back set
+// included; with a savepoint open (h->sps) every change is journaled for kh_trie_rollback.
+// The order of the stages and of their HIP calls is a measured property.
+static void forest_commit(kh_trie* h, const FCommit& F, kh_stats* stats) {
+  Commit C{h, F};
+  if (!C.begin(stats)) return;
+  C.sort_ops();        // syncs: the sort's, then the counts of tries, upserts and value bytes
+  C.place_values();
+  C.descend();
+  C.gather_elems();    // sync; may refuse (handle untouched); a short buffer: gather and sync again
+  C.value_branches();  // (sync only for a value-only branch of a handle with a write-back set)
+  C.build_elems();     // the build's own syncs; a handle with stubs: sync, may refuse (untouched)
+  C.early_roots();
+  C.values_now();      // (no element build: the producer still finishes before the commit does)
+  C.write_records();
+  C.write_back_set();
+  C.finish(stats);     // sync: roots and flags on the host
 }
 
 // ---- versioned commits: savepoint / rollback / release (see Savepoint)
@@ -4402,13 +4460,7 @@ FillResult khst::commit_fill(kh_trie* h, const uint32_t* d_trie, const uint8_t* 
                              const uint64_t* d_voff, uint64_t n, const FillMode& fm,
                              const std::function<bool()>& accept) {
   int refused = 0;
-  FCommit F;
-  F.up_trie = d_trie;
-  F.up_keys = d_keys;
-  F.up_vals = d_vals;
-  F.up_voff = d_voff;
-  F.nup = n;
-  F.klen = 32;
+  FCommit F = FCommit::of(d_trie, d_keys, d_vals, d_voff, n, nullptr, nullptr, 0, 32);
   F.fill = &fm;
   F.fill_refused = &refused;
   Txn txn(h, nullptr);
@@ -5400,13 +5452,7 @@ int kh_trie_open(kh_ctx* c, const uint8_t* d_keys, uint32_t klen, const uint8_t*
     HIPCHK(hipSetDevice(c->dev));
     h = trie_new(c, flags, false);
     try {
-      FCommit F;
-      F.up_keys = d_keys;
-      F.up_vals = d_vals;
-      F.up_voff = d_voff;
-      F.nup = n;
-      F.klen = klen;
-      forest_commit(h, F, nullptr);
+      forest_commit(h, FCommit::of(nullptr, d_keys, d_vals, d_voff, n, nullptr, nullptr, 0, klen), nullptr);
     } catch (...) {
       delete h;
       h = nullptr;
@@ -5433,12 +5479,7 @@ int kh_trie_open_host(const uint8_t* keys, uint32_t klen, const uint8_t* vals, c
     H.stream_wait(c->st, H.nkp);
     kh_trie* h = trie_new(c, flags, false);
     try {
-      FCommit F;
-      F.up_keys = S.keys;
-      F.up_vals = S.vals;
-      F.up_voff = S.voff;
-      F.nup = n;
-      F.klen = klen;
+      FCommit F = FCommit::of(nullptr, S.keys, S.vals, S.voff, n, nullptr, nullptr, 0, klen);
       F.before_values = [&H] { H.wait(H.nkp + 1); };
       F.vals_ready = H.ev(H.nkp + 1);
       forest_commit(h, F, nullptr);
@@ -5452,6 +5493,12 @@ int kh_trie_open_host(const uint8_t* keys, uint32_t klen, const uint8_t* vals, c
   })
 }
 
+// kh_trie_apply and kh_trie_apply_host once their ops are on the device
+static void trie_apply(kh_trie* h, const FCommit& F, uint8_t root32[32], kh_stats* stats) {
+  forest_commit(h, F, stats);
+  if (root32) memcpy(root32, h->root, 32);
+}
+
 int kh_trie_apply(kh_trie* h, const uint8_t* d_up_keys, const uint8_t* d_up_vals, const uint64_t* d_up_voff,
                   uint64_t nup, const uint8_t* d_del_keys, uint64_t ndel, uint32_t klen, uint32_t flags,
                   uint8_t root32[32], kh_stats* stats) {
@@ -5460,16 +5507,8 @@ int kh_trie_apply(kh_trie* h, const uint8_t* d_up_keys, const uint8_t* d_up_vals
   API_TRY({
     HIPCHK(hipSetDevice(h->c->dev));
     check_flags(h, flags);
-    FCommit F;
-    F.up_keys = d_up_keys;
-    F.up_vals = d_up_vals;
-    F.up_voff = d_up_voff;
-    F.nup = nup;
-    F.del_keys = d_del_keys;
-    F.ndel = ndel;
-    F.klen = klen;
-    forest_commit(h, F, stats);
-    if (root32) memcpy(root32, h->root, 32);
+    trie_apply(h, FCommit::of(nullptr, d_up_keys, d_up_vals, d_up_voff, nup, nullptr, d_del_keys, ndel, klen), root32,
+               stats);
   })
 }
 
@@ -5485,17 +5524,8 @@ static FCommit stage_commit(kh_ctx* c, const uint32_t* up_trie, const uint8_t* u
   const uint64_t out = P.add(up_trie, up_trie ? nup * 4 : 0), odt = P.add(del_trie, del_trie ? ndel * 4 : 0);
   P.total += 64;  // (slack past the values: 8-byte word reads)
   uint8_t* b = P.send(c, c->st);
-  FCommit F;
-  F.up_trie = up_trie ? (const uint32_t*)(b + out) : nullptr;
-  F.up_keys = b + ouk;
-  F.up_vals = b + ov;
-  F.up_voff = (const uint64_t*)(b + oo);
-  F.nup = nup;
-  F.del_trie = del_trie ? (const uint32_t*)(b + odt) : nullptr;
-  F.del_keys = b + odk;
-  F.ndel = ndel;
-  F.klen = klen;
-  return F;
+  return FCommit::of(up_trie ? (const uint32_t*)(b + out) : nullptr, b + ouk, b + ov, (const uint64_t*)(b + oo), nup,
+                     del_trie ? (const uint32_t*)(b + odt) : nullptr, b + odk, ndel, klen);
 }
 
 int kh_trie_apply_host(kh_trie* h, const uint8_t* up_keys, const uint8_t* up_vals, const uint64_t* up_voff,
@@ -5506,9 +5536,8 @@ int kh_trie_apply_host(kh_trie* h, const uint8_t* up_keys, const uint8_t* up_val
     HANDLE_LOCK(h);
     HIPCHK(hipSetDevice(h->c->dev));
     check_flags(h, flags);
-    FCommit F = stage_commit(h->c, nullptr, up_keys, up_vals, up_voff, nup, nullptr, del_keys, ndel, klen);
-    forest_commit(h, F, stats);
-    if (root32) memcpy(root32, h->root, 32);
+    trie_apply(h, stage_commit(h->c, nullptr, up_keys, up_vals, up_voff, nup, nullptr, del_keys, ndel, klen), root32,
+               stats);
   })
 }
 
@@ -5542,17 +5571,8 @@ int kh_forest_apply(kh_trie* f, const uint32_t* d_up_trie, const uint8_t* d_up_k
   HANDLE_LOCK(f);
   API_TRY({
     HIPCHK(hipSetDevice(f->c->dev));
-    FCommit F;
-    F.up_trie = d_up_trie;
-    F.up_keys = d_up_keys;
-    F.up_vals = d_up_vals;
-    F.up_voff = d_up_voff;
-    F.nup = nup;
-    F.del_trie = d_del_trie;
-    F.del_keys = d_del_keys;
-    F.ndel = ndel;
-    F.klen = klen;
-    forest_commit(f, F, stats);
+    forest_commit(f, FCommit::of(d_up_trie, d_up_keys, d_up_vals, d_up_voff, nup, d_del_trie, d_del_keys, ndel, klen),
+                  stats);
     return forest_out(f, h_tries, h_roots32, cap, n_tries);
   })
 }
@@ -5610,6 +5630,14 @@ int kh_trie_savepoint_depth(const kh_trie* h, uint32_t* depth) {
   return KH_OK;
 }
 
+// kh_trie_root_of and kh_trie_root_of_host once their ops are on the device: the root, the commit undone
+static void trie_root_of(kh_trie* h, const FCommit& F, uint8_t root32[32], kh_stats* stats) {
+  Txn txn(h, nullptr);
+  forest_commit(h, F, stats);
+  if (root32) memcpy(root32, h->root, 32);
+  txn.rollback();
+}
+
 int kh_trie_root_of(kh_trie* h, const uint8_t* d_up_keys, const uint8_t* d_up_vals, const uint64_t* d_up_voff,
                     uint64_t nup, const uint8_t* d_del_keys, uint64_t ndel, uint32_t klen, uint32_t flags,
                     uint8_t root32[32], kh_stats* stats) {
@@ -5618,18 +5646,8 @@ int kh_trie_root_of(kh_trie* h, const uint8_t* d_up_keys, const uint8_t* d_up_va
   API_TRY({
     HIPCHK(hipSetDevice(h->c->dev));
     check_flags(h, flags);
-    FCommit F;
-    F.up_keys = d_up_keys;
-    F.up_vals = d_up_vals;
-    F.up_voff = d_up_voff;
-    F.nup = nup;
-    F.del_keys = d_del_keys;
-    F.ndel = ndel;
-    F.klen = klen;
-    Txn txn(h, nullptr);
-    forest_commit(h, F, stats);
-    if (root32) memcpy(root32, h->root, 32);
-    txn.rollback();
+    trie_root_of(h, FCommit::of(nullptr, d_up_keys, d_up_vals, d_up_voff, nup, nullptr, d_del_keys, ndel, klen), root32,
+                 stats);
   })
 }
 int kh_trie_root_of_host(kh_trie* h, const uint8_t* up_keys, const uint8_t* up_vals, const uint64_t* up_voff,
@@ -5640,11 +5658,8 @@ int kh_trie_root_of_host(kh_trie* h, const uint8_t* up_keys, const uint8_t* up_v
     HANDLE_LOCK(h);
     HIPCHK(hipSetDevice(h->c->dev));
     check_flags(h, flags);
-    FCommit F = stage_commit(h->c, nullptr, up_keys, up_vals, up_voff, nup, nullptr, del_keys, ndel, klen);
-    Txn txn(h, nullptr);
-    forest_commit(h, F, stats);
-    if (root32) memcpy(root32, h->root, 32);
-    txn.rollback();
+    trie_root_of(h, stage_commit(h->c, nullptr, up_keys, up_vals, up_voff, nup, nullptr, del_keys, ndel, klen), root32,
+                 stats);
   })
 }
 
@@ -5690,25 +5705,10 @@ int kh_block_commit(kh_trie* state, kh_trie* storage, const uint32_t* d_s_up_tri
     // to the parent version (Ledger.scala:237-271 discards the world state of a failed attempt)
     Txn txn(storage, state);
     // 1. every storage trie of the block (BlockWorldState.scala:243-252 -> TrieStorage.flush)
-    FCommit S;
-    S.up_trie = d_s_up_trie;
-    S.up_keys = d_s_up_keys;
-    S.up_vals = d_s_up_vals;
-    S.up_voff = d_s_up_voff;
-    S.nup = ns_up;
-    S.del_trie = d_s_del_trie;
-    S.del_keys = d_s_del_keys;
-    S.ndel = ns_del;
-    S.klen = s_klen;
+    FCommit S = FCommit::of(d_s_up_trie, d_s_up_keys, d_s_up_vals, d_s_up_voff, ns_up, d_s_del_trie, d_s_del_keys,
+                            ns_del, s_klen);
     // 3. the accounts (TrieAccounts.flush, TrieAccounts.scala:22-28)
-    FCommit A;
-    A.up_keys = d_a_up_keys;
-    A.up_vals = d_a_up_vals;
-    A.up_voff = d_a_up_voff;
-    A.nup = na_up;
-    A.del_keys = d_a_del_keys;
-    A.ndel = na_del;
-    A.klen = a_klen;
+    FCommit A = FCommit::of(nullptr, d_a_up_keys, d_a_up_vals, d_a_up_voff, na_up, nullptr, d_a_del_keys, na_del, a_klen);
     A.chk_msg = "an account upsert with a storage trie is not an account body";
     if (c->pack_for_block) S.inputs_ready = A.inputs_ready = c->pack_ev;  // (host inputs: one DMA on c->st)
     // the injection's error word (never cleared: a failing call writes its own token into it)

@@ -5,6 +5,9 @@ hipStreamSynchronize returning and the thread's next HIP call, and for every ker
 from its launch call returning to the kernel starting on the GPU.
 
   python scripts/api_trace.py gpurun_out/bch_r6d > profiles/<tag>_block_commit_host_api_50m.json
+
+With --lists after the directory, every thread also gets its ordered HIP function names and the
+names of the kernels it launched.
 """
 import collections
 import csv
@@ -22,6 +25,7 @@ def rows(d, pat):
 
 def main():
     d = sys.argv[1]
+    lists = "--lists" in sys.argv[2:]  # (to compare two builds call by call)
     gap_ns = 20e6
     api = rows(d, "*hip_api_trace.csv")
     ker = rows(d, "*kernel_trace.csv")
@@ -39,6 +43,7 @@ def main():
     calls = sorted(({"fn": r["Function"], "tid": r["Thread_Id"], "corr": r["Correlation_Id"], "s": int(r["Start_Timestamp"]),
                      "e": int(r["End_Timestamp"])} for r in api), key=lambda c: c["s"])
     by_corr = {c["corr"]: c for c in calls}
+    k_by_corr = {k["corr"]: k["name"] for k in ks}
     res = []
     for b in blocks:
         t0, t1 = b[0]["s"] - 200_000, max(k["e"] for k in b)
@@ -61,6 +66,9 @@ def main():
                             "in_hip_us": round(sum(fn_us.values()), 1),
                             "by_function_us": {k: [fn_n[k], round(v, 1)] for k, v in fn_us.most_common(12)},
                             "host_us_after_each_sync": after_sync}
+            if lists:  # what the thread called, in order, and the kernels it launched, in launch order
+                threads[tid]["functions"] = [c["fn"] for c in lst]
+                threads[tid]["kernels"] = [k_by_corr[c["corr"]] for c in lst if c["corr"] in k_by_corr]
         lat = []
         for k in b:
             c = by_corr.get(k["corr"])

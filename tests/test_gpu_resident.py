@@ -83,6 +83,57 @@ def test_commit_uses_open_hash_keys(khst, oracle):
         t.commit(ups[:1], [], hash_keys=False)
 
 
+def _ladder(r, levels=8):
+    """A target key and, for every depth below `levels` and each of the 15 other nibbles, a key
+    that shares the target's first `depth` nibbles and then takes that nibble (random tails): the
+    target's path opens `levels` full branches."""
+    def key(nibs):
+        return bytes(nibs[2 * i] << 4 | nibs[2 * i + 1] for i in range(32))
+    t = [r.randrange(16) for _ in range(64)]
+    return [key(t)] + [key(t[:d] + [x] + [r.randrange(16) for _ in range(63 - d)])
+                       for d in range(levels) for x in range(16) if x != t[d]]
+
+
+@pytest.mark.parametrize("versioned", [False, True], ids=["plain", "savepoint"])
+def test_element_buffer_guessed_short_is_gathered_again(khst, oracle, versioned):
+    """The element buffer of a fresh handle's one-op commit is sized for 4 touched records: 1 upsert
+    + 16 * 4 children + 1 trie + 16 = 82 elements.  Re-putting a ladder's target touches 8 full
+    branches and gathers 15 * 8 + 1 = 121 elements, so the buffer is carved to the exact size and
+    the gather runs again; the second commit finds the first one's touched count as its hint and
+    gathers once.  Roots and write-back sets against the oracle; under a savepoint the journal
+    takes both commits back."""
+    from khipu_amd.device import Ctx, ResidentTrie
+    # (the sizes follow Commit::place_values' guess in khst.hip, ntl_guess = max(4 * ops, 1.25 * the
+    # last commit's touched count), and carve_elems' nups + 16 * ntl + nt + 16: a change to either
+    # needs a ladder whose first re-put still gathers more than the guessed capacity)
+    r = random.Random(82)
+    ks = _ladder(r)
+    assert len(ks) == 121
+    vs = [C.storage_value(r) for _ in ks]
+    o = oracle.Trie()
+    for k, v in zip(ks, vs):
+        o.put(k, v)
+    t = ResidentTrie(Ctx(0), ks, vs)
+    first = t.root
+    assert first == o.root_hash()
+    store = dict(t.nodes())
+    o.persist().reopen()
+    if versioned:
+        assert t.savepoint() == 1
+    for i in range(2):
+        v = bytes([0x21 + i]) * (33 - i)
+        o.put(ks[0], v)
+        assert t.commit([(ks[0], v)], []) == o.root_hash(), i
+        delta = t.nodes()
+        check_delta(delta, [o], store, i)
+        store.update(delta)
+        o.persist().reopen()
+    if versioned:
+        t.rollback()
+        assert t.root == first and t.get_root() == first and len(t) == 121
+    t.close()
+
+
 def test_commit_1m_vs_full_build(khst):
     """configs[2]-style commit at 1M accounts: 20k dirty (90% updates, 5% inserts, 5%
     deletes) -> the root of a from-scratch build of the final set; only the changed
